@@ -1,6 +1,12 @@
 """Headline benchmark: env-steps/sec for humanoid.xml at 8192 worlds (BASELINE.json configs[1]), 1/2/4/8 GPUs.
 
-    python bench.py --gpus N --steps K --warmup W [--solver cg|newton|pgs] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--solver cg|newton|pgs] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed warm-up steps, times ONE window of exactly K steps and prints the headline line (`value`,
+`ms_per_step` = the milliseconds of one timed step).  Everything else below -- the NWINDOW repeats of the window and the back-to-back
+replay, `roofline` and the per-kernel traces, `other_scaling`, `steady_1000`, `configs`, `cpu_baseline` -- runs only with --full
+(the --no-* flags then switch single parts off).  --dump-outputs DIR writes what the last timed step left in Data (OUTPUT_FIELDS,
+rank 0's worlds) as DIR/<field>.npy in float32 / float64; the inputs depend only on the arguments, so two builds compare output for output.
 
 N > 1 without a torch.distributed environment: bench.py re-executes itself through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL);
@@ -12,7 +18,7 @@ the harness' Halton/OU control noise (reference cli.py:103-145, 240-297).  State
 starts.  TIMER PLACEMENT = THE REFERENCE'S (cli.py:289-292, testspeed.py:362): per step the control-noise kernel runs
 and is synchronised UNTIMED, then `step` + device synchronise is timed; `value` = all worlds of all ranks x K / MAX over ranks of the
 summed step times.  The window of exactly K steps (after W untimed warm-up steps) is bracketed by barrier + synchronize on both
-sides and measured THREE times from the same state: `value` is the median window, `windows` lists all three (box-to-box noise on
+sides; with --full it is measured THREE times from the same state: `value` is the median window, `windows` lists all three (box-to-box noise on
 this fleet is 20-40 %, run-to-run noise ~1 %: `box` carries a fingerprint -- the state-independent k_fwd_pos launch time and
 rocm-smi clocks / power when readable).  `back_to_back` = the same K steps enqueued without per-step syncs, noise inside.
 Worlds shard with no data-path collective; the only collective is the metrics all-reduce after the timed region.
@@ -20,7 +26,7 @@ Worlds shard with no data-path collective; the only collective is the metrics al
   --scaling strong 8192 worlds in total, shard_worlds(8192, rank, N) per GPU
 With N > 1 the line also carries the other mode as `other_scaling`.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline     -- dominant kernel (the solver launch): SURVEY 8(d) algorithmic HBM bytes per launch / mean launch time from
                   HIP events recorded on the launch stream (instrumented replay of the same K steps); `traffic` is null
                   unless --pmc-profile names a rocprofv3 PMC summary of THIS solver's kernel; `issue` = what actually bounds the three
@@ -168,9 +174,10 @@ def reference_window(mjw, m, d, steps, step0):
   return total
 
 
-def measure(mjw, shard, m, mjm, nworld, world_offset, steps, warmup):
-  """W untimed warm-up steps, then exactly K timed steps (barrier + synchronize on both sides), NWINDOW times from the same state.
-  Returns the Data (for the replays), a snapshot of the state at the start of the timed window and the per-rank measurement."""
+def measure(mjw, shard, m, mjm, nworld, world_offset, steps, warmup, full=False, dump=False):
+  """W untimed warm-up steps, then exactly K timed steps (barrier + synchronize on both sides); with `full` NWINDOW times from the same
+  state, followed by the same K steps back to back.  Returns the Data (for the replays), a snapshot of the state at the start of the
+  timed window (None without `full`), the per-rank measurement and, with `dump`, step_outputs() of the last timed step."""
   import torch
 
   d = mjw.make_data(mjm, nworld=nworld, nconmax=24, njmax=64)
@@ -181,11 +188,12 @@ def measure(mjw, shard, m, mjm, nworld, world_offset, steps, warmup):
   if warmup:
     mjw.timed_steps(m, d, warmup, step0=0)
   torch.cuda.synchronize()
-  snapshot = {k: getattr(d, k).numpy().copy() for k in STATE_FIELDS}
+  snapshot = {k: getattr(d, k).numpy().copy() for k in STATE_FIELDS} if full else None
   windows = []
-  for rep in range(NWINDOW):
-    for k, v in snapshot.items():
-      getattr(d, k).assign(v)
+  for rep in range(NWINDOW if full else 1):
+    if snapshot is not None:
+      for k, v in snapshot.items():
+        getattr(d, k).assign(v)
     shard.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -193,21 +201,53 @@ def measure(mjw, shard, m, mjm, nworld, world_offset, steps, warmup):
     torch.cuda.synchronize()
     shard.barrier()
     wall = time.perf_counter() - t0
+  outputs = step_outputs(d) if dump else None
   qpos = d.qpos.numpy()
   nefc, niter = np.minimum(d.nefc.numpy(), d.njmax), d.solver_niter.numpy()
   nan_worlds, ovf_worlds = float(np.isnan(qpos).any(axis=1).sum()), float((d.overflow.numpy() != 0).sum())
-  # the same K steps enqueued back to back (no per-step sync, noise kernel inside): the engine's throughput when nothing waits for it
-  for k, v in snapshot.items():
-    getattr(d, k).assign(v)
-  shard.barrier()
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  ev_ms, _ = mjw.timed_steps(m, d, steps, step0=warmup)
-  torch.cuda.synchronize()
-  shard.barrier()
-  b2b = time.perf_counter() - t0
-  res = {"windows": windows, "wall_last_window": wall, "b2b": b2b, "ev_ms": ev_ms, "nan_worlds": nan_worlds, "ovf_worlds": ovf_worlds, "nefc": nefc, "niter": niter}
-  return d, snapshot, res
+  res = {"windows": windows, "wall_last_window": wall, "nan_worlds": nan_worlds, "ovf_worlds": ovf_worlds, "nefc": nefc, "niter": niter}
+  if full:
+    # the same K steps enqueued back to back (no per-step sync, noise kernel inside): the engine's throughput when nothing waits for it
+    for k, v in snapshot.items():
+      getattr(d, k).assign(v)
+    shard.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res["ev_ms"], _ = mjw.timed_steps(m, d, steps, step0=warmup)
+    torch.cuda.synchronize()
+    shard.barrier()
+    res["b2b"] = time.perf_counter() - t0
+  return d, snapshot, res, outputs
+
+
+# What `step` hands its caller, per world: the integrated state, the controls it stepped with, the solver's outputs and counters, the
+# body poses and sensors.  --dump-outputs writes these (float32 stays float32, int32 counters become float64: exact).
+OUTPUT_FIELDS = ("time", "qpos", "qvel", "act", "ctrl", "qacc", "qacc_warmstart", "qfrc_constraint", "qfrc_actuator", "qfrc_bias", "xpos",
+                 "xquat", "sensordata", "solver_niter", "nefc", "ws_ncon", "overflow")
+DUMP_BYTES = 64 << 20
+
+
+def step_outputs(d):
+  out = {}
+  for k in OUTPUT_FIELDS:
+    a = getattr(d, k).numpy()
+    if a.size:
+      out[k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+  return out
+
+
+def write_outputs(path, outputs, world_offset):
+  """DIR/<field>.npy for every entry of step_outputs(), plus world_id.npy (the global id of each row).  Above DUMP_BYTES in all, a fixed,
+  seeded sample of the worlds is written (the same rows in every run with the same arguments)."""
+  nworld = len(outputs["qpos"])
+  per_world = sum(a.nbytes for a in outputs.values()) / nworld + 8
+  ids = np.arange(nworld)
+  if per_world * nworld > DUMP_BYTES:
+    ids = np.sort(np.random.default_rng(0).choice(nworld, int(DUMP_BYTES // per_world), replace=False))
+  os.makedirs(path, exist_ok=True)
+  for k, a in outputs.items():
+    np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a[ids]))
+  np.save(os.path.join(path, "world_id.npy"), (ids + world_offset).astype(np.float64))
 
 
 def steady_1000(mjw, m, mjm, nworld, world_offset, nstep=1000):
@@ -352,6 +392,10 @@ def main():
   ap.add_argument("--nworld", type=int, default=NWORLD, help="worlds per GPU (weak) / in total (strong)")
   ap.add_argument("--solver", default="cg", choices=sorted(SOLVERS))
   ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
+  ap.add_argument("--full", action="store_true", help="besides the headline window: its repeats and the back-to-back replay, roofline, "
+                  "other_scaling, steady_1000, configs and cpu_baseline (the --no-* flags below switch parts of it off)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the Data fields of OUTPUT_FIELDS after the last timed step "
+                  "as DIR/<field>.npy (rank 0's worlds; a fixed sample of them above 64 MB)")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-roofline", action="store_true")
   ap.add_argument("--no-steady", action="store_true", help="skip the 1000-step reference-placement figure")
@@ -367,7 +411,7 @@ def main():
 
   xml = os.path.join(ROOT, "benchmarks", "humanoid", "humanoid.xml")
   cpu = None
-  if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
+  if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline:
     cpu = cpu_baseline(xml, SOLVERS[args.solver])  # before any HIP context exists (fork-safe)
 
   import torch
@@ -389,17 +433,20 @@ def main():
       return rank * args.nworld, args.nworld
     return shard.shard_worlds(args.nworld, rank, world_size)
 
-  def run(mode):
+  def run(mode, dump=False):
     off, cnt = shard_of(mode)
-    d, snap, r = measure(mjw, shard, m, mjm, cnt, off, args.steps, args.warmup)
+    d, snap, r, outputs = measure(mjw, shard, m, mjm, cnt, off, args.steps, args.warmup, full=args.full, dump=dump)
+    if outputs is not None:
+      write_outputs(args.dump_outputs, outputs, off)
     # every window: MAX over ranks of the summed step times; counters summed over ranks
     red = [shard.reduce_metrics(w, float(cnt * args.steps), r["nan_worlds"], r["ovf_worlds"]) for w in r["windows"]]
     r["windows_max"] = [x[0] for x in red]
-    r["b2b_max"] = shard.reduce_metrics(r["b2b"], 0.0, 0.0, 0.0)[0]
+    if args.full:
+      r["b2b_max"] = shard.reduce_metrics(r["b2b"], 0.0, 0.0, 0.0)[0]
     t_med = float(np.median(r["windows_max"]))
     return d, snap, r, cnt, t_med, red[0][1], red[0][2], red[0][3]
 
-  d, snapshot, r, nworld, t_max, env_steps, nan_tot, ovf_tot = run(args.scaling)
+  d, snapshot, r, nworld, t_max, env_steps, nan_tot, ovf_tot = run(args.scaling, dump=bool(args.dump_outputs) and rank == 0)
   nefc, niter = r["nefc"], r["niter"]
   total_worlds = args.nworld * world_size if args.scaling == "weak" else args.nworld
 
@@ -414,19 +461,21 @@ def main():
                              "nconmax=24, njmax=64, key 0 + Halton/OU control noise (std 0.01, rate 0.1)",
                  "nworld_per_gpu": nworld, "nworld_total": total_worlds, "parallelism": f"worlds sharded over {world_size} GPU(s), no data-path collective"},
       "timing": "the reference's placement (cli.py:289-292): per step the control-noise kernel + sync untimed, then step + device sync timed; "
-                f"value = median of {NWINDOW} windows of exactly K steps from the same state (max over ranks per window); back_to_back = the same steps without per-step syncs",
-      "windows": [{"value": env_steps / t, "ms_per_step": 1e3 * t / args.steps} for t in r["windows_max"]],
-      "window_spread": (max(r["windows_max"]) - min(r["windows_max"])) / t_max,
-      "back_to_back": {"value": env_steps / r["b2b_max"], "ms_per_step": 1e3 * r["b2b_max"] / args.steps, "event_ms_per_step_rank0": r["ev_ms"] / args.steps,
-                       "timing": "K steps enqueued on one stream, no per-step sync, control noise inside the timed region"},
+                + (f"value = median of {NWINDOW} windows of exactly K steps from the same state (max over ranks per window); back_to_back = the same steps without per-step syncs"
+                   if args.full else "value = one window of exactly K steps (max over ranks)"),
       "converged_worlds": int(total_worlds - nan_tot), "overflow_worlds": int(ovf_tot),
       "nefc_mean": float(nefc.mean()), "nefc_p95": float(np.percentile(nefc, 95)),
       "solver_niter_mean": float(niter.mean()), "solver_niter_p95": float(np.percentile(niter, 95)),
       "reference_published_env_steps_per_s": {"value": 2729192, "note": "Newton solver, unstated NVIDIA GPU (benchmarks/README.md:48); not the same metric"},
     }
+    if args.full:
+      out["windows"] = [{"value": env_steps / t, "ms_per_step": 1e3 * t / args.steps} for t in r["windows_max"]]
+      out["window_spread"] = (max(r["windows_max"]) - min(r["windows_max"])) / t_max
+      out["back_to_back"] = {"value": env_steps / r["b2b_max"], "ms_per_step": 1e3 * r["b2b_max"] / args.steps, "event_ms_per_step_rank0": r["ev_ms"] / args.steps,
+                             "timing": "K steps enqueued on one stream, no per-step sync, control noise inside the timed region"}
 
   # ---- roofline of the dominant kernel: instrumented replay of the same K steps (rank 0) ----
-  if rank == 0 and not args.no_roofline:
+  if rank == 0 and args.full and not args.no_roofline:
     for k, v in snapshot.items():
       getattr(d, k).assign(v)
     # HIP event pairs (recorded on the launch stream, inside mjh_timed_steps) around each launch of the fused step
@@ -464,7 +513,7 @@ def main():
   del d
 
   # ---- the other scaling mode (N > 1 only): same K / W, its own Data ----
-  if world_size > 1:
+  if world_size > 1 and args.full:
     other = "strong" if args.scaling == "weak" else "weak"
     d2, _, r2, cnt2, t2, steps2, nan2, _ = run(other)
     del d2
@@ -473,7 +522,7 @@ def main():
                               "nworld_total": args.nworld * world_size if other == "weak" else args.nworld}
 
   # ---- the reference's own 1000-step measurement (rank 0's shard; N = 1 semantics) ----
-  if rank == 0 and not args.no_steady:
+  if rank == 0 and args.full and not args.no_steady:
     off, cnt = shard_of(args.scaling)
     out["steady_1000"] = steady_1000(mjw, m, mjm, cnt, off)
     if not args.no_roofline and "solve" in out["steady_1000"].get("fused_launch_us", {}):
@@ -489,7 +538,7 @@ def main():
                                 "window": "steps 1000..1050 of the rollout from key 0 (steady)", "issue": _issue_from_profile(args.pmc_profile, args.solver, "steady")}
   shard.barrier()
 
-  if rank == 0 and world_size == 1 and not args.no_configs:
+  if rank == 0 and world_size == 1 and args.full and not args.no_configs:
     out["configs"] = other_configs(mjw, only=[x for x in args.configs_only.split(",") if x] or None)
   if rank == 0 and cpu is not None:
     out["cpu_baseline"] = cpu

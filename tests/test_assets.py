@@ -1,7 +1,7 @@
 """Mesh / height-field FILE assets: binary + ASCII STL, OBJ, `maxhullvert`, PNG and binary height fields, `meshdir`.
 
 The files are written by the tests (a regular tetrahedron and a dodecahedron -- the shapes of the reference's
-test_data/meshes/{tetrahedron,dodecahedron}.stl, which are loaded too wherever /root/reference exists); a model compiled from a file
+test_data/meshes/{tetrahedron,dodecahedron}.stl, which are loaded too from their copies in tests/golden/meshes/); a model compiled from a file
 must equal the model compiled from the same vertices inline, and step like it on the GPU.
 """
 
@@ -14,7 +14,7 @@ import pytest
 import mujoco_warp_amd as mjw
 from mujoco_warp_amd import mjcf
 
-REF_MESHES = "/root/reference/mujoco_warp/test_data/meshes"
+REF_MESHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes")  # the reference's test_data/meshes/*.stl, byte for byte
 PHI = (1 + 5**0.5) / 2
 TETRA = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], dtype=np.float64)
 SA, SB = np.array([0.1, 0.12, 0.15]), np.array([0.05, 0.06, 0.08])  # anisotropic scales: a regular solid has no unique principal frame
@@ -150,7 +150,6 @@ def test_missing_mesh_file_is_an_error_only_for_colliding_geoms(tmp_path):
   assert m.nmesh == 1  # the visual mesh is not compiled (G1 / Panda rely on this: their STL files are not in the tree)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MESHES), reason="reference tree not present")
 def test_reference_stl_fixtures_load():
   """test_data/ray.xml's assets: tetrahedron.stl (4 vertices) and dodecahedron.stl (20 vertices, Blender export)."""
   v, f = mjcf.read_stl(os.path.join(REF_MESHES, "tetrahedron.stl"))

@@ -6,7 +6,7 @@ TAG=${1:-x}; shift || true
 OUT=$PWD/gpurun_out/pmcs_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-roofline --no-steady --no-configs $*"
+BENCH="python $PWD/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-roofline --no-steady --no-configs $*"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS -d $OUT/pmc_sq -o pmc -- $BENCH > $OUT/pmc_sq.log 2>&1

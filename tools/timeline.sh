@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/prof_timeline
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-roofline $*"
+BENCH="python $PWD/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-roofline $*"
 (cd /tmp && rocprofv3 --kernel-trace -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1)
 python tools/summarize_profile.py $OUT $OUT/summary.json > /dev/null 2>&1
 rm -rf $OUT/trace
