@@ -161,6 +161,10 @@ typedef struct MjhModel {
   const int* geom_dataid;       /* [ngeom] mesh id of mesh geoms, -1 otherwise (types.py:1266)                  */
   const int* mesh_vertadr; const int* mesh_vertnum; /* [nmesh] first vertex / number of vertices (types.py:1707-1709) */
   const float* mesh_vert;       /* [nmeshvert, 3] vertices in the mesh (= geom) frame; searched exhaustively by the convex narrowphase */
+  int nmesh;                    /* mesh assets (entries of mesh_vertadr / mesh_faceadr / ...) */
+  int nmeshface;                /* triangles of all meshes (types.py Model.nmeshface); > 0 selects the lane-group ray kernel (csrc/ray.hpp) */
+  const int* mesh_face;         /* [nmeshface, 3] vertex ids local to the mesh's vertex block: the triangles rays are cast against */
+  const int* mesh_faceadr;      /* [nmesh] first triangle of the mesh (its last one precedes the next mesh's first, or nmeshface) */
   /* sensors (types.py: sensor_*; csrc/sensor.hpp computes joint / actuator / ball / frame / velocimeter / gyro / subtreecom / clock) */
   int nsensor; int nsensordata;
   int nsensor_subtree; /* subtreelinvel / subtreeangmom sensors: smooth.subtree_vel runs before the sensor launch */
@@ -383,7 +387,7 @@ int mjh_dev_knob(const char* name, const char* value);
  * wavefront), "pair" (k_solve<cg>), "newton_mfma", "newton32", "cg64", "newton64", "*_ell", "tree+big", "big", "pgs", "pgs_big", "unsupported" -- so that a
  * test or a bench line can say which kernel it measured without a knob.  Static string; host only; launches nothing. */
 const char* mjh_solver_kernel(const MjhModel* m, const MjhData* d);
-#define MJH_ABI_VERSION 43
+#define MJH_ABI_VERSION 44
 /* floats of Data.ws_ccd for a model with GJK pairs (csrc/convex.hpp ccd_layout: per world the candidate list, the per-candidate result cache and the
    broadphase mask; then the counters, the convex-pair mask and the EPA hand-over records) -- what a binding that allocates Data itself must
    provide; iterations = max(ccd_iterations, epa_iterations), concap = Data.concap.  Also returns the default Data.nccdhand through *nccdhand_out

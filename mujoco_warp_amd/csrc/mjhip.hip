@@ -1119,8 +1119,19 @@ int mjh_rays(const MjhModel* m, const MjhData* d, const float* pnt, const float*
   if ((long long)d->nworld * nray > 0x7fffffffLL) return fail(MJH_E_ARG, "mjh_rays: nworld * nray exceeds 2^31 - 1 (cast the rays in several calls)");
   RayGroup gg;
   for (int i = 0; i < 6; ++i) gg.g[i] = geomgroup ? geomgroup[i] : -1.0f;
-  hipLaunchKernelGGL(k_rays, dim3((d->nworld * nray + 255) / 256), dim3(256), 0, (hipStream_t)stream, *m, *d, pnt, vec, pnt_nworld, nray, gg, flg_static, bodyexclude, dist,
-                     geomid, normal);
+  // the model decides, not the caller (csrc/ray.hpp): primitive-only -> k_rays, untouched; meshes of few triangles (at most RAY_GROUP_MIN_FACES
+  // per mesh on average) and no height field -> the same one-thread walk over ray_world_full; otherwise a lane group per ray
+  const long long nr = (long long)d->nworld * nray;
+  if (m->nhfield > 0 || (long long)m->nmeshface > (long long)RAY_GROUP_MIN_FACES * m->nmesh) {
+    constexpr int per_block = 256 / RAY_LANES;
+    hipLaunchKernelGGL(k_rays_group, dim3((unsigned)((nr + per_block - 1) / per_block)), dim3(256), 0, (hipStream_t)stream, *m, *d, pnt, vec, pnt_nworld, nray, gg, flg_static,
+                       bodyexclude, dist, geomid, normal);
+  } else if (m->nmeshface > 0)
+    hipLaunchKernelGGL(k_rays_serial_full, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *m, *d, pnt, vec, pnt_nworld, nray, gg, flg_static, bodyexclude,
+                       dist, geomid, normal);
+  else
+    hipLaunchKernelGGL(k_rays, dim3((d->nworld * nray + 255) / 256), dim3(256), 0, (hipStream_t)stream, *m, *d, pnt, vec, pnt_nworld, nray, gg, flg_static, bodyexclude, dist,
+                       geomid, normal);
   HIPCHK(hipGetLastError());
   return MJH_OK;
 }

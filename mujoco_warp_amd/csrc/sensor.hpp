@@ -169,7 +169,9 @@ __global__ void __launch_bounds__(256) k_sensor(MjhModel m, MjhData d, int stage
     const RayGroup all = {{MJ_MAXVAL, MJ_MAXVAL, MJ_MAXVAL, MJ_MAXVAL, MJ_MAXVAL, MJ_MAXVAL}};
     int g;
     V3 n;
-    v[0] = ray_world(m, d, w, ld3(d.site_xpos + ((size_t)w * m.nsite + id) * 3), V3{xm[2], xm[5], xm[8]}, all, 1, m.site_bodyid[id], g, n);
+    const V3 p = ld3(d.site_xpos + ((size_t)w * m.nsite + id) * 3), z = V3{xm[2], xm[5], xm[8]};
+    // (models with mesh triangles / height fields: the serial walk over those too -- the same choice mjh_rays makes)
+    v[0] = (m.nmeshface > 0 || m.nhfield > 0) ? ray_world_full(m, d, w, p, z, all, 1, m.site_bodyid[id], g, n) : ray_world(m, d, w, p, z, all, 1, m.site_bodyid[id], g, n);
   }
   else if (t == SENS_SUBTREECOM) put3(ld3(d.subtree_com + ((size_t)w * m.nbody + id) * 3));
   else if (t == SENS_SUBTREELINVEL) put3(ld3(d.subtree_linvel + ((size_t)w * m.nbody + id) * 3));  // (k_subtree_vel ran just before)

@@ -269,16 +269,23 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   m._heavy_pairs = int(any((int(min(gt[a], gt[b])), int(max(gt[a], gt[b]))) in ((3, 6), (6, 6), (0, 7)) for a, b in pairs) or int(getattr(mjm, "npair", 0)) > 0
                        or m._convex_pairs)
   m.heavy_colliders = m._heavy_pairs  # c_model() adds the broadphase options (they may be changed after put_model)
-  # mesh / height-field geoms a ray could hit (visible colour: the reference's _ray_eliminate keeps them, ray.py:52): rays against
-  # them are not implemented, so rays() and the rangefinder sensor refuse such models instead of silently reporting "no hit"
+  # mesh geoms a ray could hit (visible colour: the reference's _ray_eliminate keeps them, ray.py:52) whose mesh carries no triangles
+  # (Model.mesh_face; a visual mesh whose asset was never loaded has none): rays() and the rangefinder sensor refuse such a model instead
+  # of silently reporting "no hit".  Meshes with triangles and height fields are intersected (csrc/ray.hpp)
   g_rgba = np.asarray(getattr(mjm, "geom_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (ngeom, 1))), dtype=np.float64).reshape(-1, 4)
   g_mat = np.asarray(getattr(mjm, "geom_matid", np.full(ngeom, -1))).reshape(-1)
   m_rgba = np.asarray(getattr(mjm, "mat_rgba", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4)
-  m._ray_unsupported_geoms = int(sum(1 for g in range(ngeom) if int(gt[g]) in (int(types.GeomType.MESH), int(types.GeomType.HFIELD))
-                                     and (m_rgba[g_mat[g], 3] if g_mat[g] >= 0 else g_rgba[g, 3]) != 0.0))
+  g_data = np.asarray(getattr(mjm, "geom_dataid", np.full(ngeom, -1))).reshape(-1)
+  mesh_nface = _mesh_face_counts(mjm)
+  no_tri = [g for g in range(ngeom) if int(gt[g]) == int(types.GeomType.MESH) and (m_rgba[g_mat[g], 3] if g_mat[g] >= 0 else g_rgba[g, 3]) != 0.0
+            and (g_data[g] < 0 or g_data[g] >= len(mesh_nface) or mesh_nface[g_data[g]] == 0)]
+  m._ray_unsupported_geoms = len(no_tri)
+  # their geom groups (clamped to 0..5 as the ray elimination does): a rays() call whose geomgroup hides all of them is served
+  g_group = np.asarray(getattr(mjm, "geom_group", np.zeros(ngeom))).reshape(-1)
+  m._ray_unsupported_groups = sorted(set(min(5, max(0, int(g_group[g]))) for g in no_tri))
   if m._ray_unsupported_geoms and any(int(t) == 7 for t in np.asarray(getattr(mjm, "sensor_type", np.zeros(0))).reshape(-1)):
-    raise NotImplementedError("rangefinder sensor in a model with visible mesh / height-field geoms: rays against those geoms are not implemented "
-                              "(they would be reported as no hit); make them invisible to rays (rgba alpha 0) or drop the sensor")
+    raise NotImplementedError("rangefinder sensor in a model with visible mesh geoms that have no triangles (Model.mesh_face): rays against those geoms "
+                              "would be reported as no hit; make them invisible to rays (rgba alpha 0), load their mesh or drop the sensor")
   m.is_sparse = False
 
   m.nv_pad = _get_padded_sizes(nv, 1)[1]
@@ -419,6 +426,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     mat_rgba=_arr(getattr(mjm, "mat_rgba", np.zeros((0, 4))), f32).reshape(-1, 4), geom_dataid=_arr(getattr(mjm, "geom_dataid", np.full(ngeom, -1)), i32),
     mesh_vertadr=_arr(getattr(mjm, "mesh_vertadr", np.zeros(0)), i32), mesh_vertnum=_arr(getattr(mjm, "mesh_vertnum", np.zeros(0)), i32),
     mesh_vert=_arr(getattr(mjm, "mesh_vert", np.zeros((0, 3))), f32).reshape(-1, 3),
+    mesh_face=_arr(getattr(mjm, "mesh_face", np.zeros((0, 3))), i32).reshape(-1, 3), mesh_faceadr=_arr(getattr(mjm, "mesh_faceadr", np.zeros(0)), i32),
     sensor_type=_arr(getattr(mjm, "sensor_type", np.zeros(0)), i32), sensor_datatype=_arr(getattr(mjm, "sensor_datatype", np.zeros(0)), i32),
     sensor_objtype=_arr(getattr(mjm, "sensor_objtype", np.zeros(0)), i32), sensor_objid=_arr(getattr(mjm, "sensor_objid", np.zeros(0)), i32),
     sensor_reftype=_arr(getattr(mjm, "sensor_reftype", np.zeros(0)), i32), sensor_refid=_arr(getattr(mjm, "sensor_refid", np.zeros(0)), i32),
@@ -458,6 +466,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
 
     warnings.warn(f"sensor types {sorted(set(bad))} are not computed by this engine (csrc/sensor.hpp computes {sorted(supported_sensors)}): their sensordata entries are 0")
   m.nmeshvert = int(host["mesh_vert"].shape[0])
+  m.nmeshface = int(host["mesh_face"].shape[0])
   m.nmeshpoly = int(host["mesh_polyvertnum"].shape[0])
   m.nmeshgraph = int(host["mesh_graph"].shape[0])
   m.nhfield, m.nhfielddata = int(host["hfield_nrow"].shape[0]), int(host["hfield_data"].shape[0])
@@ -558,6 +567,25 @@ def _m_dense(mjm, nv):
       j = int(colind[rowadr[i] + a])
       t[i, j] = t[j, i] = rowadr[i] + a
   return t[:nv] if nv else t[:0]
+
+
+def _mesh_face_counts(mjm):
+  """Triangles per mesh of `mjm` (Model.mesh_face / mesh_faceadr; empty when the model has none), after checking that every index stays
+  inside its mesh's vertex block: the ray kernels read the vertices through them."""
+  adr = np.asarray(getattr(mjm, "mesh_faceadr", np.zeros(0)), dtype=np.int64).reshape(-1)
+  face = np.asarray(getattr(mjm, "mesh_face", np.zeros((0, 3))), dtype=np.int64).reshape(-1, 3)
+  nmesh = len(np.asarray(getattr(mjm, "mesh_vertadr", np.zeros(0))).reshape(-1))
+  if len(adr) == 0 and len(face) == 0:
+    return np.zeros(nmesh, dtype=np.int64)
+  if len(adr) != nmesh or (np.diff(np.concatenate([[0], adr, [len(face)]])) < 0).any():
+    raise ValueError("mesh_faceadr must have one non-decreasing entry per mesh, within mesh_face")
+  num = np.diff(np.concatenate([adr, [len(face)]]))
+  vnum = np.asarray(mjm.mesh_vertnum, dtype=np.int64).reshape(-1)
+  for i in range(nmesh):
+    f = face[adr[i] : adr[i] + num[i]]
+    if len(f) and (f.min() < 0 or f.max() >= vnum[i]):
+      raise ValueError(f"mesh {i}: face index outside its {vnum[i]} vertices")
+  return num
 
 
 def c_model(m: types.Model):

@@ -732,7 +732,19 @@ def _compile_mesh(verts, maxhullvert=-1, faces=None, inertia="legacy"):
     edges.extend(sorted(nbr[l]))
     edges.append(-1)
   graph = [len(hv), len(hull.simplices)] + edgeadr + hv + edges + [int(i) for tri in hull.simplices for i in tri]
-  return dict(vert=vlocal, pos=centre + com, quat=nm.mat_to_quat(v), vol=vol, unit=w / vol, aabb=np.concatenate([(lo + hi) / 2, (hi - lo) / 2]),
+  # triangles for ray casting (Model.mesh_face, indices local to this mesh's vertices): the asset's own where it has them, otherwise the
+  # hull's, oriented outwards (what MuJoCo's compiler stores for a mesh without faces); the principal frame is right handed, so the
+  # orientation carries over to vlocal
+  if faces is not None and len(faces):
+    face = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+    if face.min() < 0 or face.max() >= len(verts):
+      raise ValueError(f"mesh face index out of range (0..{len(verts) - 1})")
+  else:
+    face = np.asarray(hull.simplices, dtype=np.int32).copy()
+    P = verts[face]
+    inward = np.einsum("fk,fk->f", np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]), hull.equations[:, :3]) < 0
+    face[inward] = face[inward][:, [0, 2, 1]]
+  return dict(vert=vlocal, face=face, pos=centre + com, quat=nm.mat_to_quat(v), vol=vol, unit=w / vol, aabb=np.concatenate([(lo + hi) / 2, (hi - lo) / 2]),
               rbound=float(np.max(np.linalg.norm(vlocal, axis=1))), polys=polys, polynormal=np.array(normals), polymap=polymap, graph=graph)
 
 
@@ -1205,6 +1217,11 @@ def _compile(root, base_dir):
   m.mesh_vertadr = np.concatenate([[0], np.cumsum(m.mesh_vertnum)[:-1]]).astype(np.int32) if mesh_names else np.zeros(0, dtype=np.int32)
   m.mesh_vert = np.concatenate([mesh_compiled[n]["vert"] for n in mesh_names]).reshape(-1, 3) if mesh_names else np.zeros((0, 3))
   m.nmeshvert = len(m.mesh_vert)
+  # triangles of every mesh (rays; Model.mesh_face / mesh_faceadr, indices local to the mesh's vertex block)
+  nface = np.array([len(mesh_compiled[n]["face"]) for n in mesh_names], dtype=np.int32)
+  m.mesh_faceadr = np.concatenate([[0], np.cumsum(nface)[:-1]]).astype(np.int32) if mesh_names else np.zeros(0, dtype=np.int32)
+  m.mesh_face = np.concatenate([mesh_compiled[n]["face"] for n in mesh_names]).reshape(-1, 3).astype(np.int32) if mesh_names else np.zeros((0, 3), dtype=np.int32)
+  m.nmeshface = len(m.mesh_face)
   mds = [mesh_compiled[n] for n in mesh_names]
   glen = [len(md["graph"]) for md in mds]
   m.mesh_graphadr = np.concatenate([[0], np.cumsum(glen)[:-1]]).astype(np.int32) if mds else np.zeros(0, dtype=np.int32)

@@ -1,8 +1,11 @@
-"""Ray casting against the primitive geoms (reference ray.py:1172 ray, 1219 rays): host mirror over mjh_rays (csrc/ray.hpp).
+"""Ray casting (reference ray.py:1172 ray, 1219 rays): host mirror over mjh_rays (csrc/ray.hpp).
 
-Mesh and height-field geoms are not intersected: `rays()` and `put_model` (for a rangefinder sensor) raise NotImplementedError on a model
-that has such geoms with a visible colour (the reference's ray elimination, ray.py:52) instead of silently reporting "no hit"; there is
-no BVH / render context."""
+Primitive, mesh and height-field geoms are intersected; a model with a height field or large meshes runs the lane-group kernel, one with small meshes the one-thread walk over the same device functions, a
+primitive-only one the one-thread-per-ray kernel -- the model decides.  A visible mesh geom whose mesh has no triangles cannot be hit.  The MJCF
+loader reads a mesh asset only for colliding or mass-carrying geoms, so the visual-only shells of aloha_pot and Unitree G1 (geom group 2) are
+such geoms: `rays()` raises NotImplementedError unless the call's `geomgroup` hides every group they are in (rays are then cast against the
+collision geometry), and `put_model` raises for a rangefinder sensor (which has no group mask) -- never a silent "no hit" (the reference's ray
+elimination, ray.py:52, keeps the geom); there is no BVH / render context."""
 
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -26,8 +29,12 @@ def rays(m, d, pnt: DeviceArray, vec: DeviceArray, geomgroup: Optional[Sequence[
   if rc is not None:
     raise NotImplementedError("render contexts (BVH-accelerated mesh / flex rays) are not part of this engine")
   if getattr(m, "_ray_unsupported_geoms", 0):
-    raise NotImplementedError(f"{m._ray_unsupported_geoms} mesh / height-field geom(s) can be hit by rays in this model: rays against them are not "
-                              "implemented (they would silently report no hit); give those geoms rgba alpha 0 if rays are meant to pass through them")
+    groups = getattr(m, "_ray_unsupported_groups", list(range(6)))
+    masked = geomgroup is not None and len(geomgroup) == 6 and not all(float(x) == -1 for x in geomgroup) and all(float(geomgroup[g]) == 0 for g in groups)
+    if not masked:
+      raise NotImplementedError(f"{m._ray_unsupported_geoms} visible mesh geom(s) of this model (geom group(s) {groups}) have no triangles (Model.mesh_face: the loader "
+                                "reads a mesh asset only for colliding or mass-carrying geoms): rays would silently pass through them; hide their group(s) with "
+                                "geomgroup, or give those geoms rgba alpha 0, if that is meant")
   if len(pnt.shape) != 3 or pnt.shape[2] != 3 or tuple(pnt.shape) != tuple(vec.shape):
     raise ValueError(f"pnt {pnt.shape} and vec {vec.shape} must both be [1 or nworld, nray, 3]")
   if pnt.shape[0] not in (1, d.nworld):

@@ -454,6 +454,11 @@ class Model(_Dirty):
   mesh_vertadr: DeviceArray = _arr(('nmesh',), "int32")
   mesh_vertnum: DeviceArray = _arr(('nmesh',), "int32")
   mesh_vert: DeviceArray = _arr(('nmeshvert', 3), "float32")
+  # triangles of the meshes, for rays (reference types.py Model.mesh_face / mesh_faceadr / nmeshface): mesh_face is [nmeshface, 3] int32, vertex ids
+  # local to the mesh's vertex block (declared without a symbolic shape: nmeshface is not among the sizes the schema check evaluates)
+  mesh_face: DeviceArray = dataclasses.field(default=None, repr=False, metadata={"dtype": "int32", "host": False})
+  mesh_faceadr: DeviceArray = _arr(('nmesh',), "int32")
+  nmeshface: int = 0
   nmeshvert: int = 0
   nmeshpoly: int = 0
   nmeshpolyvert: int = 0
