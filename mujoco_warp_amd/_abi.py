@@ -231,6 +231,7 @@ def lib():
     if needs_build():
       raise RuntimeError(f"libmjhip.so still does not match the sources after a rebuild (library {library_build_id()}, sources {source_build_id()})")
   # MJH_LIB: developer knob to A/B two builds of the same ABI in one GPU session (tools/ab.sh)
+  _env_knobs.update(k for k in os.environ if k.startswith("MJH_") and k != "MJH_LIB")  # (what the library's snapshot sees)
   L = ctypes.CDLL(os.environ.get("MJH_LIB", LIB_PATH))
   mp, dp, vp = ctypes.POINTER(CModel), ctypes.POINTER(CData), ctypes.c_void_p
   L.mjh_stage.argtypes = [mp, dp, ctypes.c_int, vp]
@@ -269,26 +270,42 @@ class EngineError(RuntimeError):
   pass
 
 
+_knob_values = {}  # what this process set through set_knob (the ABI has no getter: dev_knobs restores from here)
+_env_knobs = set()  # MJH_* names the library found in the environment when it was loaded
+
+
 def set_knob(name, value):
   """The library's one test hook (mjh_dev_knob, include/mjhip.h): set (str / int) or clear (None) a developer knob of the loaded library.  The
-  library never reads the environment after it was loaded, so os.environ has no effect on a running process."""
+  library never reads the environment after it was loaded, so os.environ has no effect on a running process.  A latched knob (read once at
+  its first use: DESIGN.md 3.1) that has been read raises EngineError."""
   check(lib().mjh_dev_knob(name.encode(), None if value is None else str(value).encode()))
+  if value is None:
+    _knob_values.pop(name, None)
+  else:
+    _knob_values[name] = str(value)
 
 
 class dev_knobs:
-  """with dev_knobs(MJH_CG_KERNEL="pair"): ...  -- knobs set for the block (tests, A/B tools), cleared afterwards."""
+  """with dev_knobs(MJH_CG_KERNEL="pair"): ...  -- knobs set for the block (tests, A/B tools); afterwards each is back at what this process
+  had set before the block (nested blocks unwind), or unset.  A value that came from the environment could not be restored (no getter in
+  the ABI), so shadowing one raises EngineError instead of silently losing it."""
 
   def __init__(self, **kv):
     self.kv = kv
 
   def __enter__(self):
+    lib()
+    for k in self.kv:
+      if k in _env_knobs and k not in _knob_values:
+        raise EngineError(f"dev_knobs: {k} is set in the environment and would not be restored; unset it or use set_knob")
+    self.prev = {k: _knob_values.get(k) for k in self.kv}
     for k, v in self.kv.items():
       set_knob(k, v)
     return self
 
   def __exit__(self, *a):
-    for k in self.kv:
-      set_knob(k, None)
+    for k, v in self.prev.items():
+      set_knob(k, v)
 
 
 def check(rc):

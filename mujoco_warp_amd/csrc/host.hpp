@@ -1,10 +1,13 @@
 // host.hpp -- host-side helpers shared by the translation units of libmjhip.so.
 //
 // The library is built from several translation units compiled in parallel (the solver kernels are ~70 template
-// instantiations and dominate the build time): mjhip.hip (entry points, launch sequencing, every non-solver kernel),
-// solve_cg32 / solve_newton32 / solve_cg64 / solve_newton64 .hip and their elliptic-cone twins solve_ell_*.hip (k_solve_plus
-// instantiations), pgs_tu.hip (k_solve_pgs) and
-// solve_big.hip (k_solve_big).
+// instantiations and dominate the build time; _abi.UNITS and unity.hip list them):
+//   mjhip.hip                          entry points, the step plan, launch sequencing, every non-solver kernel
+//   solve_cg32 / solve_cg64 / solve_newton32 / solve_newton64 .hip, their elliptic-cone twins solve_ell_*.hip and the
+//   one-row-per-lane solve_ell_newton32_r1.hip       k_solve_plus instantiations (solve_newton32.hip also k_solve_newton, MFMA)
+//   solve_cgp.hip / solve_cgw.hip      k_solve_cgp_plus (pooled contact-basis CG) / k_solve_cgw_plus (one world per wavefront)
+//   solve_tree_cg / solve_tree_newton / solve_tree_ell_cg / solve_tree_ell_newton .hip   k_solve_tree (per-island solves, nv > 64)
+//   pgs_tu.hip (k_solve_pgs, k_solve_pgs_big), solve_big.hip (k_solve_big), build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,9 +17,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mjhip.h"
+#include "dev_common.hpp"
 
 int mjh_fail(int code, const char* fmt, const char* a = "");  // records the message for mjh_last_error (mjhip.hip)
 #define fail mjh_fail
@@ -28,10 +33,71 @@ int mjh_fail(int code, const char* fmt, const char* a = "");  // records the mes
 
 static const int kLdsPerCU = 160 * 1024;
 
-// Developer knobs (tuning / A-B switches; none changes results beyond what the parity tests bound).  The MJH_* environment variables are
-// read ONCE, when the library is loaded, into a table (mjhip.hip); nothing on the launch path calls getenv.  mjh_dev_knob (include/mjhip.h)
-// -- the one documented test hook -- overrides an entry of the table afterwards.  Returns nullptr when the knob is unset.
+// Developer knobs (tuning / A-B switches; none changes results beyond what the parity tests bound; DESIGN.md lists every one).  The MJH_*
+// environment variables are read ONCE, when the library is loaded, into a table (mjhip.hip); nothing on the launch path calls getenv.
+// mjh_dev_knob (include/mjhip.h) -- the one documented test hook -- overrides an entry of the table afterwards.  mjh_knob returns nullptr
+// when the knob is unset (lock-free while the table is empty); the string it returns is interned and stays valid for the process.
+// Two kinds of reader, told apart at the call site:
+//   knob_str / knob_flag / knob_int     LIVE: looked up on every call, so mjh_dev_knob takes effect at the next launch
+//   KNOB_ONCE_INT / KNOB_ONCE_FLAG      LATCHED: read at first use (one static per call site) and registered, so that a later mjh_dev_knob
+//                                       on that name fails with MJH_E_ARG instead of silently doing nothing
 const char* mjh_knob(const char* name);
+void mjh_knob_latch(const char* name);
+static inline const char* knob_str(const char* name) { return mjh_knob(name); }
+static inline bool knob_flag(const char* name) { return mjh_knob(name) != nullptr; }
+static inline int knob_int(const char* name, int dflt) {
+  const char* v = mjh_knob(name);
+  return v ? atoi(v) : dflt;
+}
+#define KNOB_ONCE_INT(name, dflt) ([] { static const int v_ = (mjh_knob_latch(name), knob_int(name, dflt)); return v_; }())
+#define KNOB_ONCE_FLAG(name) ([] { static const bool v_ = (mjh_knob_latch(name), knob_flag(name)); return v_; }())
+
+// friction cones are elliptic AND some contact has more than one row (condim 1 everywhere: the cone type is moot)
+static inline bool elliptic(const MjhModel* m, const MjhData* d) { return m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1; }
+
+// ceil(nv / 4) as a compile-time constant: kernels are specialised on it (no padded matrix columns).  f is a generic lambda called with a
+// std::integral_constant, e.g. dispatch_nv4_32(nv4, [&](auto NV4) { return launch_cgp_t<NV4()>(m, d, ...); }).  Two ladders, so that a
+// launcher instantiates the sizes of its own lane count only: 32 lanes per world (nv <= 32: 1 .. 8) ...
+template <typename F>
+static inline int dispatch_nv4_32(int nv4, F&& f) {
+  switch (nv4) {
+    case 0:
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+// ... and 64 lanes per world (32 < nv <= 64), rounded up to an instantiated size (lanes past nv hold identity rows)
+template <typename F>
+static inline int dispatch_nv4_64(int nv4, F&& f) {
+  if (nv4 <= 9) return f(std::integral_constant<int, 9>{});
+  if (nv4 <= 10) return f(std::integral_constant<int, 10>{});
+  if (nv4 <= 12) return f(std::integral_constant<int, 12>{});
+  if (nv4 <= 14) return f(std::integral_constant<int, 14>{});
+  return f(std::integral_constant<int, 16>{});
+}
+
+// Profiling builds only (hipcc -DMJH_PHASE_CLOCK; tools/build_variant_fast.py, tools/phase_clock.py --lib ...): read (and optionally reset)
+// the per-kernel, per-phase tick sums.  Every unit that marks phases has its own copy of g_phase_ticks (dev_common.hpp) and therefore
+// exports its own copy of this reader: MJH_DEFINE_PHASE_TICKS at the end of the unit.
+#ifdef MJH_PHASE_CLOCK
+#define MJH_DEFINE_PHASE_TICKS                                                                                                      \
+  extern "C" __attribute__((visibility("default"))) int mjh_debug_phase_ticks(unsigned long long* out, int reset) {               \
+    if (out) HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_ticks), sizeof(unsigned long long) * 64 * 8 * 16));                 \
+    if (reset) {                                                                                                                    \
+      static unsigned long long zeros[64 * 8 * 16] = {0};                                                                           \
+      HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zeros, sizeof(zeros)));                                                   \
+    }                                                                                                                               \
+    return MJH_OK;                                                                                                                  \
+  }
+#else
+#define MJH_DEFINE_PHASE_TICKS
+#endif
 
 // pick threads per block in {256,128,64} maximising resident worlds per CU for the given LDS needs (mjhip.hip)
 int pick_block(size_t shared_bytes, size_t per_world_bytes, int G, size_t* lds_out, bool prefer_small_arg = false);
@@ -54,8 +120,7 @@ static hipError_t set_lds(K kernel, size_t bytes) {
 // developer knob MJH_DEBUG_OCC: print the resident workgroups per CU the runtime computes for a launch and the rounds its grid needs
 template <typename K>
 static void debug_occupancy(const char* name, K kernel, int grid, int threads, size_t lds) {
-  static const bool on = mjh_knob("MJH_DEBUG_OCC") != nullptr;
-  if (!on) return;
+  if (!KNOB_ONCE_FLAG("MJH_DEBUG_OCC")) return;
   int nb = -1;
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds);
   fprintf(stderr, "%-22s grid %5d x %3d threads, LDS %6zu B: %2d workgroups per CU = %4.1f wavefronts per SIMD, %.2f rounds on 256 CUs\n", name, grid,
@@ -73,7 +138,10 @@ int launch_solve_cgw(const MjhModel* m, const MjhData* d, bool with_factor, int 
 // are flagged solver_niter = -1 for the fallback launch (launch_solve_32_cg_deferred, solve_cg32.hip)
 int launch_solve_32_cg_deferred(const MjhModel* m, const MjhData* d, int fuse_euler, hipStream_t s);
 int launch_solve_cgp(const MjhModel* m, const MjhData* d, bool with_factor, int fuse_euler, hipStream_t s);
+// Newton, nv <= 32, pyramidal cones: the register-resident VALU solver (k_solve_plus) and the MFMA kernel (solver_newton.hpp: njmax <= 64, every
+// world of the batch, 32-bit byte offsets; with_factor: the riders as its trailing workgroups).  plan_step (mjhip.hip) decides which one runs.
 int launch_solve_32_newton(const MjhModel* m, const MjhData* d, int nr, bool with_factor, int fuse_euler, hipStream_t s, int lo, int hi);
+int launch_solve_newton_mfma(const MjhModel* m, const MjhData* d, bool with_factor, int fuse_euler, hipStream_t s);
 int launch_solve_64_cg(const MjhModel* m, const MjhData* d, int nr, bool with_factor, int fuse_euler, hipStream_t s, int lo, int hi);
 int launch_solve_64_newton(const MjhModel* m, const MjhData* d, int nr, bool with_factor, int fuse_euler, hipStream_t s, int lo, int hi);
 // the same with elliptic friction cones (solve_ell_*.hip)
@@ -87,6 +155,8 @@ int launch_solve_tree_cg(const MjhModel* m, const MjhData* d, hipStream_t s, hip
 int launch_solve_tree_newton(const MjhModel* m, const MjhData* d, hipStream_t s, hipStream_t sr, hipStream_t sr2, hipStream_t sr3);
 int launch_solve_tree_cg_ell(const MjhModel* m, const MjhData* d, hipStream_t s, hipStream_t sr, hipStream_t sr2, hipStream_t sr3);      // (elliptic cones: solve_tree_ell_*.hip)
 int launch_solve_tree_newton_ell(const MjhModel* m, const MjhData* d, hipStream_t s, hipStream_t sr, hipStream_t sr2, hipStream_t sr3);
+// PGS: the register / LDS resident sweeps (pgs.hpp: nv <= 64, pyramidal cones) and the generic kernel (pgs_big.hpp: nv > 64 or elliptic cones)
 int launch_pgs(const MjhModel* m, const MjhData* d, hipStream_t s);
+int launch_pgs_big(const MjhModel* m, const MjhData* d, hipStream_t s);
 // generic LDS solver (solver_big.hpp): nv > 64, and the worlds of a small model with more than nefc_lo = 192 rows
 int launch_solve_big(const MjhModel* m, const MjhData* d, hipStream_t s, int nefc_lo = -1);

@@ -394,10 +394,13 @@ DEV void schedule_body(const MjhData& d, int* sh, int nthreads, int cls = 0) {
 // one world per wavefront: there a solve's length follows the row count (the Hessian build) more than the iteration count, and "worlds of more
 // than 64 rows first" is the longest-first order (G1, 4096 worlds: 8.2 M env-steps/s with the classes, 6.9 M without -- measured in round 5
 // when the classes were dropped for every model).
+// (host twin: sched_cls_host below -- keep the two in step)
 DEV int sched_cls(const MjhModel& m, const MjhData& d) {
   if (m.nv > 32) return 64;
   return (m.solver == SOL_NEWTON && m.cone == CONE_ELLIPTIC && d.njmax > 32) ? 32 : 0;
 }
+// the host's twin of sched_cls above, for the plain path's k_schedule_worlds launch (mjhip.hip run_stage) -- keep the two in step
+static inline int sched_cls_host(const MjhModel& m, const MjhData& d) { return m.nv > 32 ? 64 : ((m.solver == SOL_NEWTON && m.cone == CONE_ELLIPTIC && d.njmax > 32) ? 32 : 0); }
 __global__ void __launch_bounds__(1024) k_schedule_worlds(MjhData d, int cls) {
   __shared__ int sh[512];
   schedule_body(d, sh, blockDim.x, cls);

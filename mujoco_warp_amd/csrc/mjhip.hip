@@ -37,18 +37,22 @@ int mjh_fail(int code, const char* fmt, const char* a) {
 // ---- developer knobs: a table filled ONCE from the environment when the library is loaded; mjh_dev_knob overrides entries (host.hpp) ----
 #include <atomic>
 #include <map>
+#include <set>
 #include <string>
 extern char** environ;
 namespace {
 struct KnobTable {
   std::mutex mu;
-  std::map<std::string, std::string> kv;  // (node-based: a value's storage does not move when other keys are added)
+  std::set<std::string> pool;                    // every value ever set, interned: what mjh_knob hands out is never freed
+  std::map<std::string, const std::string*> kv;  // name -> its value in `pool`
+  std::set<std::string> latched;                 // names a KNOB_ONCE_* reader has consumed (mjh_dev_knob refuses them)
   std::atomic<int> n{0};
+  void set(const std::string& name, const char* value) { kv[name] = &*pool.insert(value).first; }
   KnobTable() {
     for (char** e = environ; e && *e; ++e) {
-      if (strncmp(*e, "MJH_", 4) != 0) continue;
+      if (strncmp(*e, "MJH_", 4) != 0 || strncmp(*e, "MJH_LIB=", 8) == 0) continue;  // (MJH_LIB: the Python loader's variable, not a knob)
       const char* eq = strchr(*e, '=');
-      if (eq) kv[std::string(*e, eq - *e)] = std::string(eq + 1);
+      if (eq) set(std::string(*e, eq - *e), eq + 1);
     }
     n.store((int)kv.size());
   }
@@ -66,7 +70,12 @@ const char* mjh_knob(const char* name) {
   if (t.n.load(std::memory_order_acquire) == 0) return nullptr;  // the product path: no knob set, no lock, no lookup
   std::lock_guard<std::mutex> lock(t.mu);
   auto it = t.kv.find(name);
-  return it == t.kv.end() ? nullptr : it->second.c_str();
+  return it == t.kv.end() ? nullptr : it->second->c_str();
+}
+void mjh_knob_latch(const char* name) {
+  KnobTable& t = knobs();
+  std::lock_guard<std::mutex> lock(t.mu);
+  t.latched.insert(name);
 }
 #define TRY(x)               \
   do {                       \
@@ -76,7 +85,7 @@ const char* mjh_knob(const char* name) {
 
 // pick threads per block in {256,128,64} maximising resident worlds per CU for the given LDS needs
 int pick_block(size_t shared_bytes, size_t per_world_bytes, int G, size_t* lds_out, bool prefer_small_arg) {
-  static const int small_env = mjh_knob("MJH_SMALL_BLOCKS") ? atoi(mjh_knob("MJH_SMALL_BLOCKS")) : -1;  // developer knob
+  const int small_env = KNOB_ONCE_INT("MJH_SMALL_BLOCKS", -1);  // developer knob
   const bool prefer_small = small_env >= 0 ? (small_env != 0) : prefer_small_arg;
   int best = 0, best_worlds = -1;
   // ties go to the first candidate: large blocks amortise the block-shared tables, small blocks retire as soon as
@@ -105,7 +114,7 @@ int pick_block(size_t shared_bytes, size_t per_world_bytes, int G, size_t* lds_o
 // and bodies, 64 beyond (round 3): these kernels are chains of dependent steps whose loops stride over dofs / bodies / geoms by the
 // group size, so a model that needs two trips with 32 lanes needs one with 64 (three humanoids, nv 81: k_mid 690 -> 518 us, step + 22 %).
 static inline bool lanes64(const MjhModel* m) {
-  static const int force = mjh_knob("MJH_LANES") ? atoi(mjh_knob("MJH_LANES")) : 0;  // developer knob: 32 / 64
+  const int force = KNOB_ONCE_INT("MJH_LANES", 0);  // developer knob: 32 / 64
   if (force) return force == 64;
   // (models with GJK / EPA pairs stay at 32: Data.ws_ccd holds one polytope workspace per lane of a 32-lane group)
   return (m->nv > 32 || m->nbody > 32) && !m->heavy_colliders;
@@ -115,8 +124,8 @@ static inline bool lanes64(const MjhModel* m) {
 // (- 8.7 %).  Not for larger models (humanoid, 27 dofs on 17 bodies, forced with MJH_LANES16_ANY: k_mid 84 -> 101 us -- every loop needs two
 // trips) and not for k_fwd_pos (Panda 48.0 vs 49.1 us: its chain is the tree depth whatever the lane count; MJH_LANES16_POS turns it on).
 static inline bool lanes16(const MjhModel* m) {
-  static const int force = mjh_knob("MJH_LANES") ? atoi(mjh_knob("MJH_LANES")) : 0;  // developer knob: 16 / 32 / 64
-  static const bool any = mjh_knob("MJH_LANES16_ANY") != nullptr;
+  const int force = KNOB_ONCE_INT("MJH_LANES", 0);  // developer knob: 16 / 32 / 64
+  const bool any = KNOB_ONCE_FLAG("MJH_LANES16_ANY");
   if (force && force != 16) return false;
   return ((m->nv <= 16 && m->nbody <= 16) || (force == 16 && any)) && !m->heavy_colliders;
 }
@@ -184,8 +193,8 @@ static int launch_ccd_pre(const MjhModel* m, const MjhData* d, hipStream_t s) {
   {
     // lanes per pair by the length of the list (read on the device): one lane per pair needs >= 2 wavefronts per SIMD to hide its chains of
     // dependent table loads; shorter lists give a pair 8 or 32 lanes (MJH_GJK_LANES: developer knob, forces one instantiation)
-    static const int force = mjh_knob("MJH_GJK_LANES") ? atoi(mjh_knob("MJH_GJK_LANES")) : 0;
-    static const int t8_env = mjh_knob("MJH_GJK_T8") ? atoi(mjh_knob("MJH_GJK_T8")) : 16384, t1_env = mjh_knob("MJH_GJK_T1") ? atoi(mjh_knob("MJH_GJK_T1")) : 131072;  // developer knobs
+    const int force = KNOB_ONCE_INT("MJH_GJK_LANES", 0);
+    const int t8_env = KNOB_ONCE_INT("MJH_GJK_T8", 16384), t1_env = KNOB_ONCE_INT("MJH_GJK_T1", 131072);  // developer knobs
     const int all = 0x7fffffff, t8 = force ? (force == 32 ? all : 0) : t8_env, t1 = force ? (force == 1 ? 0 : all) : std::max(t1_env, t8_env);
     const long long cap = (long long)d->nworld * CL.ccap;  // work items at most
     const int grid1 = (int)std::min<long long>((cap + 255) / 256, 2048);
@@ -195,7 +204,7 @@ static int launch_ccd_pre(const MjhModel* m, const MjhData* d, hipStream_t s) {
   }
   // lane groups per workgroup: a group's LDS (polytope + the multi-contact polygon buffers: 11.7 KB on the ALOHA scene) decides how many are
   // resident on a CU -- eight groups in one 256-thread workgroup leave room for ONE workgroup there; smaller workgroups pack the LDS
-  static const int epa_threads = mjh_knob("MJH_EPA_THREADS") ? atoi(mjh_knob("MJH_EPA_THREADS")) : 256;  // developer knob
+  const int epa_threads = KNOB_ONCE_INT("MJH_EPA_THREADS", 256);  // developer knob
   const size_t group_bytes = sizeof(float) * (size_t)ccd_coop_words(it, m->npolygonmax, m->nmeshdegmax);
   int gpb = std::max(epa_threads / G, 1);
   while (gpb > 1 && group_bytes * gpb > (size_t)kLdsPerCU) gpb >>= 1;  // (a mesh vertex of very high degree: long feature lists per group)
@@ -399,7 +408,7 @@ static int launch_mid_g(const MjhModel* m, const MjhData* d, bool sched, hipStre
     else --nw_v;
   }
   if (nw_v < 1) nw_v = 1;
-  if (const char* e = mjh_knob("MJH_MID_W")) {  // tuning knob (developer only): worlds per workgroup of both roles
+  if (const char* e = knob_str("MJH_MID_W")) {  // tuning knob (developer only): worlds per workgroup of both roles
     nw_cc = nw_v = atoi(e);
     lds = sizeof(float) * stride_cc * nw_cc;
   }
@@ -417,7 +426,8 @@ static int launch_mid_g(const MjhModel* m, const MjhData* d, bool sched, hipStre
   else HIPCHK(set_lds((k_mid<G, false>), lds));
   const int ncc = (d->nworld + nw_cc - 1) / nw_cc, nvb = (d->nworld + nw_v - 1) / nw_v;
   const dim3 grid(ncc + nvb + (sched ? 1 : 0)), block(G * std::max(nw_cc, nw_v));
-  if (m->heavy_colliders) debug_occupancy("k_mid<heavy>", k_mid<G, true>, (int)grid.x, (int)block.x, lds);
+  if (m->heavy_colliders && hf) debug_occupancy("k_mid<heavy>", k_mid<G, true, true>, (int)grid.x, (int)block.x, lds);
+  else if (m->heavy_colliders) debug_occupancy("k_mid<heavy>", k_mid<G, true, false>, (int)grid.x, (int)block.x, lds);
   else debug_occupancy("k_mid", k_mid<G, false>, (int)grid.x, (int)block.x, lds);
   if (m->heavy_colliders && hf) hipLaunchKernelGGL((k_mid<G, true, true>), grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
   else if (m->heavy_colliders) hipLaunchKernelGGL((k_mid<G, true, false>), grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
@@ -426,10 +436,6 @@ static int launch_mid_g(const MjhModel* m, const MjhData* d, bool sched, hipStre
   }
 }
 static int launch_mid(const MjhModel* m, const MjhData* d, bool sched, hipStream_t s) { return lanes16(m) ? launch_mid_g<16>(m, d, sched, s) : lanes64(m) ? launch_mid_g<64>(m, d, sched, s) : launch_mid_g<32>(m, d, sched, s); }
-// set by the fused STEP path when the solver launch also integrates (see euler_fusable)
-static thread_local int g_fuse_euler = 0;  // 1: explicit Euler, 2: implicitfast in the solver's epilogue
-// set by the fused path when the Newton riders run on the side stream (see side_stream)
-static thread_local bool g_riders_on_side = false;
 static int solve_supported(const MjhModel* m, const MjhData* d) {
   if (m->cone != CONE_PYRAMIDAL && m->cone != CONE_ELLIPTIC) return fail(MJH_E_UNSUPPORTED, "unknown cone type");
   if (m->solver != SOL_NEWTON && m->solver != SOL_CG && m->solver != SOL_PGS) return fail(MJH_E_UNSUPPORTED, "unknown solver");
@@ -449,8 +455,7 @@ struct Aux {
 static thread_local Aux* g_aux_per_dev[16] = {nullptr};
 static thread_local bool g_serial_solver = false;  // set while per-kernel instrumentation is on (one stream, one event pair per launch)
 static Aux* aux_streams() {
-  static const bool disabled = mjh_knob("MJH_NO_AUX") != nullptr;  // developer knob
-  if (disabled || g_serial_solver) return nullptr;
+  if (KNOB_ONCE_FLAG("MJH_NO_AUX") || g_serial_solver) return nullptr;  // (developer knob)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   if (!g_aux_per_dev[dev]) {
@@ -466,143 +471,117 @@ static Aux* aux_streams() {
   }
   return g_aux_per_dev[dev];
 }
-// The Newton riders as trailing workgroups of the MFMA solver launch (solver_newton.hpp) instead of a side-stream launch, for SMALL models
-// (round 3).  Where the solve is short the side stream's fork / join hops and the riders' late start set the step: Panda (nv 9, njmax 5: solver
-// 22 us) 135.0 -> 117.2 us per step (60.7 -> 69.9 M env-steps/s, two interleaved pairs on one box).  Where the solve is long the riders'
-// workgroups in its tail cost more than the join they save: humanoid (nv 27) 0.2824 / 0.2844 -> 0.2894 / 0.2897 ms, so the side stream stays
-// above 16 dofs.  Applies exactly when launch_solve_32_newton picks the MFMA kernel.  MJH_NEWTON_RIDERS=0 / 1 forces it off / on (developer knob).
-static thread_local bool g_newton_inline = false;
-static bool newton_inline_ok(const MjhModel* m, const MjhData* d) {
-  static const int force = mjh_knob("MJH_NEWTON_RIDERS") ? atoi(mjh_knob("MJH_NEWTON_RIDERS")) : -1;
-  static const bool old_path = mjh_knob("MJH_OLD_NEWTON") != nullptr;
-  const bool ell = m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1;
-  const bool want = force >= 0 ? force != 0 : m->nv <= 16;
-  return want && !old_path && m->solver == SOL_NEWTON && !ell && m->nv <= 32 && d->njmax <= 64 && (double)d->nworld * std::max(m->nv, d->njmax) * 4.0 < 4.0e9;
-}
-// Which CG kernel serves the class nv <= 32, pyramidal cones (the ONE place that decides; mjh_solver_kernel reports it).
-//   CG32_CGW  one world per wavefront (solver_cgw.hpp): SMALL batches.  A solve is a dependent chain of ~17 k instructions per wavefront of which
+// ---- the step plan: every decision of a step that more than one launch depends on, taken ONCE ---------------------------------------
+// plan_step is the one place that decides which solver kernel serves (m, d) and where the public-output riders (contact publication, L'DL
+// factor + qacc_smooth) go; run_stage passes the plan down, launch_solve_any switches on it, mjh_solver_kernel reports it.  Pure: nothing
+// is launched, no stream is touched, nothing allocated.
+// Adding a solver kernel touches: one SolverFamily value + its string, one branch in plan_step, one branch in launch_solve_any, one launcher
+// declaration in host.hpp, one unit in _abi.UNITS and unity.hip.
+enum SolverFamily { FAM_UNSUPPORTED, FAM_PGS, FAM_PGS_BIG, FAM_BIG, FAM_TREE_BIG, FAM_CG64, FAM_CG64_ELL, FAM_NEWTON64, FAM_NEWTON64_ELL,
+                    FAM_NEWTON_MFMA, FAM_NEWTON32, FAM_NEWTON32_ELL, FAM_CG32_ELL, FAM_CGW, FAM_CGP, FAM_PAIR };
+static const char* const kFamilyName[] = {"unsupported", "pgs", "pgs_big", "big", "tree+big", "cg64", "cg64_ell", "newton64", "newton64_ell",
+                                          "newton_mfma", "newton32", "newton32_ell", "cg32_ell", "cgw", "cgp", "pair"};
+// who carries the riders: nobody (the stage API: its plain kernels), trailing workgroups of the solver launch (CG; Newton "inline", MFMA kernel
+// only), a launch of their own on the side stream beside the solver (Newton), or the integrator launch
+enum Riders { RIDE_NONE, RIDE_SOLVER, RIDE_SIDE, RIDE_INTEGRATOR };
+struct StepPlan {
+  int mode;        // integrator: 0 Euler, 1 implicitfast, 2 implicit (k_integrate's argument)
+  int fuse_euler;  // the solver's epilogue integrates: 0 no (the integrator launch does), 1 explicit Euler, 2 implicitfast
+  Riders riders;
+  SolverFamily family;
+  bool newton, ell;  // (ell: elliptic(m, d))
+  bool r1;           // Newton, elliptic cones: the one-row-per-lane launch for the worlds of at most 32 rows goes first
+};
+static inline int integrator_mode(const MjhModel* m) { return m->integrator == INT_IMPLICITFAST ? 1 : (m->integrator == INT_IMPLICIT ? 2 : 0); }  // (k_integrate's argument)
+static SolverFamily plan_family(const MjhModel* m, const MjhData* d, bool ell, int fuse_euler) {
+  if (solve_supported(m, d)) return FAM_UNSUPPORTED;
+  const bool newton = m->solver == SOL_NEWTON;
+  if (m->solver == SOL_PGS) return m->nv > 64 || ell ? FAM_PGS_BIG : FAM_PGS;
+  if (m->nv > 64) return m->tree_solve ? FAM_TREE_BIG : FAM_BIG;
+  // the k_solve_plus instantiations: by lanes per world (32 up to 32 dofs, 64 beyond), solver and cone
+  if (m->nv > 32) return newton ? (ell ? FAM_NEWTON64_ELL : FAM_NEWTON64) : (ell ? FAM_CG64_ELL : FAM_CG64);
+  if (newton) {
+    if (ell) return FAM_NEWTON32_ELL;
+    // the MFMA kernel (solver_newton.hpp) takes every world of a batch with njmax <= 64; 32-bit byte offsets inside the kernel: nworld *
+    // max(nv, njmax) * 4 must fit.  MJH_OLD_NEWTON (developer knob): A/B against the VALU solver
+    const bool mfma = !KNOB_ONCE_FLAG("MJH_OLD_NEWTON") && d->njmax <= 64 && (double)d->nworld * std::max(m->nv, d->njmax) * 4.0 < 4.0e9;
+    return mfma ? FAM_NEWTON_MFMA : FAM_NEWTON32;
+  }
+  if (ell) return FAM_CG32_ELL;
+  // Which CG kernel serves the class nv <= 32, pyramidal cones:
+//   cgw       one world per wavefront (solver_cgw.hpp): SMALL batches.  A solve is a dependent chain of ~17 k instructions per wavefront of which
 //             the line search's per-wavefront bookkeeping is the bulk, so pairing two worlds in a wavefront halves the instruction count per world
 //             and wins whenever the SIMDs are issue bound (measured, humanoid: 8192 worlds 194 us one-per-wavefront vs 193 paired, 141 M vs 81 M
 //             VALU instructions); with at most ~3 wavefronts per SIMD the chain's latency decides instead and the shorter chain of the unpaired
 //             kernel wins (1024 worlds: 88 vs 112 us, 2048: 103 vs 120, 3072: 122 vs 124)
-//   CG32_CGP  the pooled contact-basis kernel (solver_cgp.hpp): larger batches of models whose contacts are condim 1 / 3 and that have no
+//   cgp       the pooled contact-basis kernel (solver_cgp.hpp): larger batches of models whose contacts are condim 1 / 3 and that have no
 //             friction-loss rows (MjhModel.cg_basis), njmax <= 64
-//   CG32_PAIR k_solve<cg> (solver.hpp): everything else
-// MJH_CG_KERNEL = cgp / pair / cgw (developer knob; tests set it through mjh_dev_knob) forces one of the three where it applies.
-enum { CG32_PAIR = 0, CG32_CGW = 1, CG32_CGP = 2 };
-static int cg32_choice(const MjhModel* m, const MjhData* d, int fe) {
-  const bool newton = m->solver == SOL_NEWTON, ell = m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1;
-  if (newton || ell || m->solver == SOL_PGS || m->nv > 32) return CG32_PAIR;
-  static const int wide_min_nv = mjh_knob("MJH_CGW_MIN_NV") ? atoi(mjh_knob("MJH_CGW_MIN_NV")) : 13;
-  static const int wide_max_nworld = mjh_knob("MJH_CGW_MAX_NWORLD") ? atoi(mjh_knob("MJH_CGW_MAX_NWORLD")) : 3072;
-  const bool wide = m->nv >= wide_min_nv && d->nworld <= wide_max_nworld && fe != 2;  // (its half rows of M do not serve the fused implicitfast update)
+//   pair      k_solve<cg> (solver.hpp): everything else
+  // MJH_CG_KERNEL = cgp / pair / cgw (developer knob, live; tests set it through mjh_dev_knob) forces one of the three where it applies.
+  const bool wide_can = fuse_euler != 2;  // (its half rows of M do not serve the fused implicitfast update)
+  const bool wide = m->nv >= KNOB_ONCE_INT("MJH_CGW_MIN_NV", 13) && d->nworld <= KNOB_ONCE_INT("MJH_CGW_MAX_NWORLD", 3072) && wide_can;
   const bool cgp_can = m->cg_basis && d->njmax <= 64 && m->nv >= 1;
-  const char* force = mjh_knob("MJH_CG_KERNEL");
-  if (force && !strcmp(force, "cgw")) return fe != 2 ? CG32_CGW : CG32_PAIR;
-  if (force && !strcmp(force, "pair")) return CG32_PAIR;
-  if (force && !strcmp(force, "cgp")) return cgp_can ? CG32_CGP : CG32_PAIR;
-  return wide ? CG32_CGW : (cgp_can ? CG32_CGP : CG32_PAIR);
+  const char* force = knob_str("MJH_CG_KERNEL");
+  if (force && !strcmp(force, "cgw")) return wide_can ? FAM_CGW : FAM_PAIR;
+  if (force && !strcmp(force, "pair")) return FAM_PAIR;
+  if (force && !strcmp(force, "cgp")) return cgp_can ? FAM_CGP : FAM_PAIR;
+  return wide ? FAM_CGW : (cgp_can ? FAM_CGP : FAM_PAIR);
+}
+// stage: MJH_STAGE_STEP / MJH_STAGE_FORWARD plan the fused launches; any other stage plans a bare solve (the stage API, the plain path, the sleep path)
+// instrumented: per-kernel event pairs are on (one stream, no side launches).  side_ok = false: the side stream could not be created
+static StepPlan plan_step(const MjhModel* m, const MjhData* d, int stage, bool instrumented, bool side_ok = true) {
+  StepPlan p;
+  p.mode = integrator_mode(m);
+  p.newton = m->solver == SOL_NEWTON;
+  p.ell = elliptic(m, d);
+  p.fuse_euler = 0;
+  p.riders = RIDE_NONE;
+  if (stage == MJH_STAGE_STEP || stage == MJH_STAGE_FORWARD) {
+    const bool step = stage == MJH_STAGE_STEP;
+    // The Newton riders as trailing workgroups of the MFMA solver launch (solver_newton.hpp) instead of a side-stream launch, for SMALL models
+    // (round 3).  Where the solve is short the side stream's fork / join hops and the riders' late start set the step: Panda (nv 9, njmax 5: solver
+    // 22 us) 135.0 -> 117.2 us per step (60.7 -> 69.9 M env-steps/s, two interleaved pairs on one box).  Where the solve is long the riders'
+    // workgroups in its tail cost more than the join they save: humanoid (nv 27) 0.2824 / 0.2844 -> 0.2894 / 0.2897 ms, so the side stream stays
+    // above 16 dofs.  Only with the MFMA kernel.  MJH_NEWTON_RIDERS=0 / 1 forces it off / on (developer knob).
+    const int inl_force = KNOB_ONCE_INT("MJH_NEWTON_RIDERS", -1);
+    const bool inl = step && !instrumented && (inl_force >= 0 ? inl_force != 0 : m->nv <= 16) && plan_family(m, d, p.ell, 0) == FAM_NEWTON_MFMA;
+    // Newton only: the riders cannot ride with the solver launch of larger models (its 256 VGPRs throttle them) and cost 55 us at the end of the
+    // integrator launch; they run on a low-priority side stream beside the solver instead (see side_stream)
+    // (nv <= 32 only: beside the 64-lane solver of larger models the riders cost more than they save, G1 -3 %)
+    const bool side = p.newton && m->nv <= KNOB_ONCE_INT("MJH_SIDE_NV", 32) && !instrumented && !inl && side_ok && !KNOB_ONCE_FLAG("MJH_NO_SIDE");  // developer knobs
+    p.riders = inl || (m->solver == SOL_CG && m->nv <= 64) ? RIDE_SOLVER : side ? RIDE_SIDE : RIDE_INTEGRATOR;
+    // explicit Euler without activations: the velocity/position update is a few loads and stores per dof, done by the
+    // solver's own epilogue (saves a launch); every other case keeps the integrator workgroups
+    // (Newton: only when its riders run with the solver or on the side stream -- otherwise the integrator launch exists anyway, for them)
+    const bool fusable = step && m->na == 0 && p.riders != RIDE_INTEGRATOR && m->nv <= 64 &&
+                         m->nsensor_acc == 0 &&  // (acceleration-stage sensors read qvel / qacc between the solver and the integrator)
+                         d->njmax <= 192;        // (beyond: some worlds go to the generic solver, which does not integrate)
+    // implicitfast without activations (round 3): the dense system (M + h D - h dA/dv) x = M qacc is solved from the M row the solver holds
+    // (MJH_NO_FUSE_IMPLICITFAST: developer knob, A/B)
+    p.fuse_euler = !fusable ? 0
+                   : (m->integrator == INT_EULER && (m->disableflags & (DSBL_EULERDAMP | DSBL_DAMPER)) != 0) ? 1
+                   : (m->integrator == INT_IMPLICITFAST && !KNOB_ONCE_FLAG("MJH_NO_FUSE_IMPLICITFAST") && !m->act_velfeedback) ? 2 : 0;  // (positive velocity feedback: the matrix may be indefinite -- the integrator launch's L'DL handles that, the epilogue's Cholesky does not)
+  }
+  p.family = plan_family(m, d, p.ell, p.fuse_euler);
+  // rows per lane (32 lanes per world): 1 covers 32 rows, 2 covers 64 rows (humanoid, panda), 6 covers 192.  Newton with elliptic cones has
+  // a one-row instantiation for the worlds of at most 32 rows (the ALOHA scene: nefc 24 on average, 27 at the 95th percentile): 155 instead
+  // of 191 VGPRs and 6.7 instead of 12.2 KB of LDS per world -- 2.9 instead of 1.6 wavefronts per SIMD -- and half the row work per lane:
+  // 333 -> 254 us per step there (MJH_SOLVE_R1=0: developer knob, off).  The launches follow one another on the caller's stream: a batch
+  // with worlds in both classes pays the latency of one more solve (on a side stream beside the 64-row launch the ALOHA scene LOST 17 %:
+  // 4.95 vs 5.97 M env-steps/s, the fork / join hops inside the step's graph).  (The same for CG with pyramidal cones was built and
+  // measured on the humanoid -- bit-identical results, but no gain: behind one another 0.471 vs 0.369 ms per step at nefc 46 where a
+  // quarter of the worlds are in the small class; side by side 0.370 vs 0.372 ms there and 0.349 vs 0.329 ms at nefc 32.  Not kept.)
+  p.r1 = p.family == FAM_NEWTON32_ELL && d->njmax > 32 && KNOB_ONCE_INT("MJH_SOLVE_R1", 1) != 0;
+  return p;
 }
 #ifndef MJH_SOLVE64_SPLIT_DEFAULT
 #define MJH_SOLVE64_SPLIT_DEFAULT 0
 #endif
-static int launch_solve_any(const MjhModel* m, const MjhData* d, bool with_factor, hipStream_t s) {
-  if (int rc = solve_supported(m, d)) return rc;
-  if (m->solver == SOL_NEWTON) with_factor = with_factor && g_newton_inline;
-  if (m->nv > 64) {  // no riders: they go with the integrator launch
-    if (m->solver == SOL_PGS) return launch_pgs(m, d, s);  // (the generic PGS kernel: csrc/pgs_big.hpp)
-    if (m->tree_solve) {
-      // constraint islands (trees joined by coupling rows): worlds whose islands all have at most 64 dofs are solved per island by the
-      // register-resident kernels, the others by the generic solver below
-      hipLaunchKernelGGL(k_isl_clear, dim3(1), dim3(64), 0, s, *d);
-      hipLaunchKernelGGL(k_tree_rows, dim3(d->nworld), dim3(64), sizeof(int) * (size_t)(2 * std::max(d->njmax, 1) + 2 * m->ntree), s, *m, *d);
-      const bool ell_t = m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1;
-      Aux* aux = aux_streams();
-      // One stream per rare island class (round 6).  clutter_synth, 2048 worlds, steps 100-300 (tools/clutter_ab.py, bit-identical states, two
-      // interleaved rounds): hipGraph replay -- the reference's own way to run a step, cli.py:262-290 -- none 1.27, one shared side stream 1.29,
-      // one each 1.43 M env-steps/s; eager launches 1.28 / 1.28 / 1.40.  (Eager, steps 0-100 -- five trees awake, every class launch nearly
-      // empty -- the forks are host API calls on the critical path: 1.74 / 1.48 / 1.51; the graph replay does not pay them: 1.75 / 1.73 / 1.78.)
-      int naux = 0;
-      if (aux) {
-        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-        naux = (hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusActive) ? MJH_NAUX : MJH_NAUX_EAGER;
-        static const int cap = mjh_knob("MJH_NAUX") ? atoi(mjh_knob("MJH_NAUX")) : -1;  // developer knob (A/B): 2 = one side stream for the rare classes, 4 = one each
-        if (cap >= 2 && cap <= MJH_NAUX) naux = cap;
-      }
-      // stream 0: islands of 8..16 dofs; 1: the generic solver (worlds with an island beyond 64 dofs); 2: 16..32 dofs; 3: many rows / 33..64 dofs.
-      // MJH_BIG_SHARES=1 (developer knob, A/B): the generic solver behind the 16..32-dof class on stream 2 -- four branches instead of five (the
-      // runtime has four hardware queues by default: R6.7).  Measured, two interleaved rounds: clutter_synth 1.55 / 1.54, three_humanoids
-      // 5.18 / 5.17 M env-steps/s -- nothing; off.
-      static const bool big_shares = mjh_knob("MJH_BIG_SHARES") && atoi(mjh_knob("MJH_BIG_SHARES")) != 0;
-      const bool share = big_shares && naux > 2;
-      bool used[MJH_NAUX] = {false, false, false, false};
-      for (int k = 0; k < naux; ++k) used[k] = !(share && k == 1);
-      hipStream_t s1 = aux ? aux->stream[0] : s, s3 = naux > 2 ? aux->stream[2] : s1, s4 = naux > 3 ? aux->stream[3] : s1;
-      hipStream_t s2 = !aux ? s : (share ? s3 : aux->stream[1]);
-      if (aux) {
-        HIPCHK(hipEventRecord(aux->fork, s));
-        for (int k = 0; k < naux; ++k)
-          if (used[k]) HIPCHK(hipStreamWaitEvent(aux->stream[k], aux->fork, 0));
-      }
-      int rc = (m->solver == SOL_NEWTON ? (ell_t ? launch_solve_tree_newton_ell : launch_solve_tree_newton) : (ell_t ? launch_solve_tree_cg_ell : launch_solve_tree_cg))(m, d, s, s1, s3, s4);
-      if (!rc) rc = launch_solve_big(m, d, s2);
-      if (aux) {  // (every fork rejoins the caller's stream, also on the error path: the streams may be under capture)
-        for (int k = 0; k < naux; ++k) {
-          if (!used[k]) continue;
-          HIPCHK(hipEventRecord(aux->join[k], aux->stream[k]));
-          HIPCHK(hipStreamWaitEvent(s, aux->join[k], 0));
-        }
-      }
-      return rc;
-    }
-    return launch_solve_big(m, d, s);
-  }
-  if (m->solver == SOL_PGS) return launch_pgs(m, d, s);
-  const bool newton = m->solver == SOL_NEWTON;
-  const int fe = g_fuse_euler;
-  const int all = 0x7fffffff;
-  // the k_solve_plus instantiations live in their own translation units (host.hpp): pick by lanes per world and solver
-  const bool ell = m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1;  // (condim 1 everywhere: the cone type is moot)
-  auto s32 = ell ? (newton ? launch_solve_32_newton_ell : launch_solve_32_cg_ell) : (newton ? launch_solve_32_newton : launch_solve_32_cg);
-  auto s64 = ell ? (newton ? launch_solve_64_newton_ell : launch_solve_64_cg_ell) : (newton ? launch_solve_64_newton : launch_solve_64_cg);
-  // njmax > 64: two launches over the same world list (see solve_body): a small-row instantiation for the worlds with
-  // at most 64 rows, the big one (riders attached) for the rest
-  // njmax > 192: the register-resident kernels end at 192 rows (6 x 32 / 3 x 64 lanes); the (rare) worlds beyond go to the generic
-  // solver, which keeps J in HBM and is generic in njmax
-  const int top = d->njmax > 192 ? 192 : all;
-  if (m->nv <= 32) {
-    const int cgk = cg32_choice(m, d, fe);  // (above)
-    const bool wide_f = cgk == CG32_CGW, cgp = cgk == CG32_CGP;
-    // rows per lane (32 lanes per world): 1 covers 32 rows, 2 covers 64 rows (humanoid, panda), 6 covers 192.  Newton with elliptic cones has
-    // a one-row instantiation for the worlds of at most 32 rows (the ALOHA scene: nefc 24 on average, 27 at the 95th percentile): 155 instead
-    // of 191 VGPRs and 6.7 instead of 12.2 KB of LDS per world -- 2.9 instead of 1.6 wavefronts per SIMD -- and half the row work per lane:
-    // 333 -> 254 us per step there (MJH_SOLVE_R1=0: developer knob, off).  The launches follow one another on the caller's stream: a batch
-    // with worlds in both classes pays the latency of one more solve (on a side stream beside the 64-row launch the ALOHA scene LOST 17 %:
-    // 4.95 vs 5.97 M env-steps/s, the fork / join hops inside the step's graph).  (The same for CG with pyramidal cones was built and
-    // measured on the humanoid -- bit-identical results, but no gain: behind one another 0.471 vs 0.369 ms per step at nefc 46 where a
-    // quarter of the worlds are in the small class; side by side 0.370 vs 0.372 ms there and 0.349 vs 0.329 ms at nefc 32.  Not kept.)
-    static const bool r1_on = !mjh_knob("MJH_SOLVE_R1") || atoi(mjh_knob("MJH_SOLVE_R1")) != 0;
-    const bool r1 = r1_on && newton && ell && d->njmax > 32;
-    int lo2 = -1;
-    if (r1) {
-      if (int rc = launch_solve_32_newton_ell_r1(m, d, false, fe, s, -1, 32)) return rc;
-      lo2 = 32;
-    }
-    // CG, pyramidal, contacts of condim 1 / 3, njmax <= 64 (the headline class): contact-basis rows in one row pool per workgroup, three
-    // wavefronts per SIMD (solver_cgp.hpp); the worlds it flags (a contact cut by njmax, a pool overflow) are solved by k_solve<cg> in the
-    // launch behind it, which is empty in the common case.
-    if (cgp) {
-      if (int rc = launch_solve_cgp(m, d, with_factor, fe, s)) return rc;
-      return launch_solve_32_cg_deferred(m, d, fe, s);
-    }
-    auto rest = [&, wide = wide_f]() -> int {
-      if (d->njmax <= 64) return wide ? launch_solve_cgw(m, d, with_factor, fe, s, -1, all) : s32(m, d, 2, with_factor, fe, s, lo2, all);
-      if (int rc = wide ? launch_solve_cgw(m, d, false, fe, s, -1, 64) : s32(m, d, 2, false, fe, s, lo2, 64)) return rc;
-      if (int rc = s32(m, d, 6, with_factor, fe, s, 64, top)) return rc;
-      return d->njmax > 192 ? launch_solve_big(m, d, s, 192) : MJH_OK;
-    };
-    return rest();
-  }
+// the launches of the 64-lane families (32 < nv <= 64): k_solve_plus by rows per lane
+static int launch_solve_rows_64(const MjhModel* m, const MjhData* d, const StepPlan& p, hipStream_t s) {
+  const int fe = p.fuse_euler, all = 0x7fffffff, top = d->njmax > 192 ? 192 : all;  // (top: see launch_solve_any)
+  const bool with_factor = p.riders == RIDE_SOLVER;
+  auto s64 = p.ell ? (p.newton ? launch_solve_64_newton_ell : launch_solve_64_cg_ell) : (p.newton ? launch_solve_64_newton : launch_solve_64_cg);
   // 64 lanes per world: 1 / 2 / 3 rows per lane cover 64 / 128 / 192 rows.  The second launch of a pair runs after the
   // first on the same stream, so the split point is chosen to leave it (almost) empty: its real worlds would otherwise
   // be a serial tail on an idle GPU (G1: 6 % of the worlds exceed 64 rows, practically none exceed 128)
@@ -610,7 +589,7 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, bool with_facto
   // (developer knob MJH_SOLVE64_R1=1: the worlds of at most 64 rows by the one-row instantiation -- half the J tile -- in a launch of their own.
   // Measured on the G1 replay, 4096 worlds, nefc 68 on average: bit-identical states, 7.84 vs 9.14 M env-steps/s -- a second launch with real
   // worlds costs the latency of one more solve.  Off.)
-  static const bool r1_64 = mjh_knob("MJH_SOLVE64_R1") && atoi(mjh_knob("MJH_SOLVE64_R1")) != 0;
+  const bool r1_64 = KNOB_ONCE_INT("MJH_SOLVE64_R1", 0) != 0;
   int lo64 = -1;
   if (r1_64) {
     if (int rc = s64(m, d, 1, false, fe, s, -1, 64)) return rc;
@@ -619,7 +598,7 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, bool with_facto
   // Round 6: the same split with the two launches BESIDE one another (an auxiliary stream, fork / join through events).  The kernel is bound by
   // LDS per world (one-row instantiation 12.6 KB, two-row 23.7 KB: 8 against 6 worlds per CU on the G1), so the few-row worlds at their own
   // size shorten the batch by a partial round -- as long as they do not wait for the many-row launch.  MJH_SOLVE64_SPLIT=0 / 1 (developer knob).
-  static const int split_knob = mjh_knob("MJH_SOLVE64_SPLIT") ? atoi(mjh_knob("MJH_SOLVE64_SPLIT")) : MJH_SOLVE64_SPLIT_DEFAULT;
+  const int split_knob = KNOB_ONCE_INT("MJH_SOLVE64_SPLIT", MJH_SOLVE64_SPLIT_DEFAULT);
   Aux* aux64 = (split_knob && !r1_64) ? aux_streams() : nullptr;
   if (aux64) {
     HIPCHK(hipEventRecord(aux64->fork, s));
@@ -641,42 +620,116 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, bool with_facto
   // Round 6: a launch's J tile is sized for the rows it can meet (solve_layout(min(njmax, hi))).  Lowering the two-row launch's bound to 112 rows
   // fits one more G1 world per CU (19.3 instead of 21.7 KB: 8 instead of 7) -- measured, two interleaved rounds, bit-identical states: 9.54 M
   // env-steps/s at 128, 9.47 at 112, 9.44 at 96: the launch is not bound by whole LDS rounds.  The bound stays 128; MJH_SOLVE64_HI2 (developer knob).
-  static const int hi2_knob = mjh_knob("MJH_SOLVE64_HI2") ? atoi(mjh_knob("MJH_SOLVE64_HI2")) : 0;
+  const int hi2_knob = KNOB_ONCE_INT("MJH_SOLVE64_HI2", 0);
   const int hi2 = (hi2_knob >= 80 && hi2_knob <= 128) ? (hi2_knob & ~15) : 128;
   if (int rc = s64(m, d, 2, with_factor, fe, s, lo64, hi2)) return rc;
   if (int rc = s64(m, d, 3, false, fe, s, hi2, top)) return rc;
   return d->njmax > 192 ? launch_solve_big(m, d, s, 192) : MJH_OK;
 }
-static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s) { return launch_solve_any(m, d, false, s); }
-static int launch_solve_plus(const MjhModel* m, const MjhData* d, hipStream_t s) { return launch_solve_any(m, d, true, s); }
-// name of the solver mapping launch_solve_any picks for (m, d) in a fused step -- the decision functions above, nothing launched
-static const char* solver_kernel_name(const MjhModel* m, const MjhData* d) {
-  if (solve_supported(m, d)) return "unsupported";
-  if (m->solver == SOL_PGS) return m->nv > 64 || (m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1) ? "pgs_big" : "pgs";
-  if (m->nv > 64) return m->tree_solve ? "tree+big" : "big";
-  const bool newton = m->solver == SOL_NEWTON, ell = m->cone == CONE_ELLIPTIC && d->nmaxpyramid > 1;
-  if (m->nv > 32) return newton ? (ell ? "newton64_ell" : "newton64") : (ell ? "cg64_ell" : "cg64");
-  if (newton) return ell ? "newton32_ell" : (d->njmax <= 64 ? "newton_mfma" : "newton32");
-  if (ell) return "cg32_ell";
-  const int fe = (m->integrator == INT_EULER || m->integrator == INT_IMPLICITFAST) ? 1 : 0;  // (only fe == 2 changes the choice, and only for cgw)
-  switch (cg32_choice(m, d, fe)) {
-    case CG32_CGW: return "cgw";
-    case CG32_CGP: return "cgp";
-    default: return "pair";
+// the launches of the plan's solver family (fe: the solver's epilogue integrates; with_factor: the riders are its trailing workgroups)
+static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan& p, hipStream_t s) {
+  const int fe = p.fuse_euler, all = 0x7fffffff;
+  const bool with_factor = p.riders == RIDE_SOLVER;
+  // njmax > 192: the register-resident kernels end at 192 rows (6 x 32 / 3 x 64 lanes); the (rare) worlds beyond go to the generic
+  // solver, which keeps J in HBM and is generic in njmax
+  const int top = d->njmax > 192 ? 192 : all;
+  switch (p.family) {
+    case FAM_UNSUPPORTED: return solve_supported(m, d);  // (its code and message)
+    case FAM_PGS: return launch_pgs(m, d, s);
+    case FAM_PGS_BIG: return launch_pgs_big(m, d, s);  // (the generic PGS kernel: csrc/pgs_big.hpp)
+    case FAM_BIG: return launch_solve_big(m, d, s);    // (nv > 64: no riders, they go with the integrator launch)
+    case FAM_TREE_BIG: {
+      // constraint islands (trees joined by coupling rows): worlds whose islands all have at most 64 dofs are solved per island by the
+      // register-resident kernels, the others by the generic solver below
+      hipLaunchKernelGGL(k_isl_clear, dim3(1), dim3(64), 0, s, *d);
+      hipLaunchKernelGGL(k_tree_rows, dim3(d->nworld), dim3(64), sizeof(int) * (size_t)(2 * std::max(d->njmax, 1) + 2 * m->ntree), s, *m, *d);
+      Aux* aux = aux_streams();
+      // One stream per rare island class (round 6).  clutter_synth, 2048 worlds, steps 100-300 (tools/clutter_ab.py, bit-identical states, two
+      // interleaved rounds): hipGraph replay -- the reference's own way to run a step, cli.py:262-290 -- none 1.27, one shared side stream 1.29,
+      // one each 1.43 M env-steps/s; eager launches 1.28 / 1.28 / 1.40.  (Eager, steps 0-100 -- five trees awake, every class launch nearly
+      // empty -- the forks are host API calls on the critical path: 1.74 / 1.48 / 1.51; the graph replay does not pay them: 1.75 / 1.73 / 1.78.)
+      int naux = 0;
+      if (aux) {
+        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+        naux = (hipStreamIsCapturing(s, &cst) == hipSuccess && cst == hipStreamCaptureStatusActive) ? MJH_NAUX : MJH_NAUX_EAGER;
+        const int cap = KNOB_ONCE_INT("MJH_NAUX", -1);  // developer knob (A/B): 2 = one side stream for the rare classes, 4 = one each
+        if (cap >= 2 && cap <= MJH_NAUX) naux = cap;
+      }
+      // stream 0: islands of 8..16 dofs; 1: the generic solver (worlds with an island beyond 64 dofs); 2: 16..32 dofs; 3: many rows / 33..64 dofs.
+      // MJH_BIG_SHARES=1 (developer knob, A/B): the generic solver behind the 16..32-dof class on stream 2 -- four branches instead of five (the
+      // runtime has four hardware queues by default: R6.7).  Measured, two interleaved rounds: clutter_synth 1.55 / 1.54, three_humanoids
+      // 5.18 / 5.17 M env-steps/s -- nothing; off.
+      const bool big_shares = KNOB_ONCE_INT("MJH_BIG_SHARES", 0) != 0;
+      const bool share = big_shares && naux > 2;
+      bool used[MJH_NAUX] = {false, false, false, false};
+      for (int k = 0; k < naux; ++k) used[k] = !(share && k == 1);
+      hipStream_t s1 = aux ? aux->stream[0] : s, s3 = naux > 2 ? aux->stream[2] : s1, s4 = naux > 3 ? aux->stream[3] : s1;
+      hipStream_t s2 = !aux ? s : (share ? s3 : aux->stream[1]);
+      if (aux) {
+        HIPCHK(hipEventRecord(aux->fork, s));
+        for (int k = 0; k < naux; ++k)
+          if (used[k]) HIPCHK(hipStreamWaitEvent(aux->stream[k], aux->fork, 0));
+      }
+      int rc = (p.newton ? (p.ell ? launch_solve_tree_newton_ell : launch_solve_tree_newton) : (p.ell ? launch_solve_tree_cg_ell : launch_solve_tree_cg))(m, d, s, s1, s3, s4);
+      if (!rc) rc = launch_solve_big(m, d, s2);
+      if (aux) {  // (every fork rejoins the caller's stream, also on the error path: the streams may be under capture)
+        for (int k = 0; k < naux; ++k) {
+          if (!used[k]) continue;
+          HIPCHK(hipEventRecord(aux->join[k], aux->stream[k]));
+          HIPCHK(hipStreamWaitEvent(s, aux->join[k], 0));
+        }
+      }
+      return rc;
+    }
+    case FAM_NEWTON_MFMA: return launch_solve_newton_mfma(m, d, with_factor, fe, s);
+    case FAM_CGP: {
+      // CG, pyramidal, contacts of condim 1 / 3, njmax <= 64 (the headline class): contact-basis rows in one row pool per workgroup, three
+      // wavefronts per SIMD (solver_cgp.hpp); the worlds it flags (a contact cut by njmax, a pool overflow) are solved by k_solve<cg> in the
+      // launch behind it, which is empty in the common case.
+      if (int rc = launch_solve_cgp(m, d, with_factor, fe, s)) return rc;
+      return launch_solve_32_cg_deferred(m, d, fe, s);
+    }
+    case FAM_CGW:
+    case FAM_PAIR:
+    case FAM_CG32_ELL:
+    case FAM_NEWTON32:
+    case FAM_NEWTON32_ELL: {
+      // 32 lanes per world, 2 rows per lane cover 64 rows, 6 cover 192 (the one-row launch of plan.r1: see plan_step)
+      auto s32 = p.ell ? (p.newton ? launch_solve_32_newton_ell : launch_solve_32_cg_ell) : (p.newton ? launch_solve_32_newton : launch_solve_32_cg);
+      const bool wide = p.family == FAM_CGW;
+      int lo2 = -1;
+      if (p.r1) {
+        if (int rc = launch_solve_32_newton_ell_r1(m, d, false, fe, s, -1, 32)) return rc;
+        lo2 = 32;
+      }
+      // njmax > 64: two launches over the same world list (see solve_body): a small-row instantiation for the worlds with
+      // at most 64 rows, the big one (riders attached) for the rest
+      if (d->njmax <= 64) return wide ? launch_solve_cgw(m, d, with_factor, fe, s, -1, all) : s32(m, d, 2, with_factor, fe, s, lo2, all);
+      if (int rc = wide ? launch_solve_cgw(m, d, false, fe, s, -1, 64) : s32(m, d, 2, false, fe, s, lo2, 64)) return rc;
+      if (int rc = s32(m, d, 6, with_factor, fe, s, 64, top)) return rc;
+      return d->njmax > 192 ? launch_solve_big(m, d, s, 192) : MJH_OK;
+    }
+    case FAM_CG64:
+    case FAM_CG64_ELL:
+    case FAM_NEWTON64:
+    case FAM_NEWTON64_ELL: return launch_solve_rows_64(m, d, p, s);
   }
+  return fail(MJH_E_ARG, "launch_solve_any: unknown solver family");
 }
-// integrator (optional) + publication of the contact arrays + solver schedule
+static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s) { return launch_solve_any(m, d, plan_step(m, d, MJH_STAGE_SOLVE, false), s); }  // (the bare solve: no riders, no fused integrator)
+// name of the solver family of (m, d) in a fused step -- the plan, nothing launched
+static const char* solver_kernel_name(const MjhModel* m, const MjhData* d) { return kFamilyName[plan_step(m, d, MJH_STAGE_STEP, false).family]; }
+// integrator workgroups (integrate) and the riders -- contact publication, L'DL factor + qacc_smooth -- (with_factor)
 template <int G>
-static int launch_integrate_plus_g(const MjhModel* m, const MjhData* d, int mode, bool integrate, hipStream_t s) {
+static int launch_integrate_plus_g(const MjhModel* m, const MjhData* d, int mode, bool integrate, bool with_factor, hipStream_t s) {
   const IntLayout lay = int_layout(m->nv, m->nC);
   const FacLayout fl = fac_layout(m->nv, m->nC);
   const size_t ms_bytes = sizeof(int) * mstruct_ints(m->nv, m->nC);
-  const bool with_factor = (m->solver != SOL_CG || m->nv > 64) && !g_riders_on_side;
   size_t lds = std::max(ms_bytes + sizeof(float) * std::max(lay.total, fl.total) * (256 / G), (size_t)2048);
   if (lds > (size_t)kLdsPerCU) return fail(MJH_E_UNSUPPORTED, "k_integrate: does not fit in LDS");
   HIPCHK(set_lds(k_integrate_plus<G>, lds));
   const int nb = (d->nworld + 256 / G - 1) / (256 / G);
-  // Newton: publication and factor workgroups ride here; CG: they already rode with the solver launch
+  // (the riders: here when the plan says RIDE_INTEGRATOR, and on the side stream, as a launch without integrator workgroups)
   const int nint = integrate ? nb : 0, npub = with_factor ? nb : 0, nfac = with_factor ? nb : 0;
   if (nint + npub + nfac == 0) return MJH_OK;
   if (integrate && mode == 2) TRY(launch_implicit(m, d, s));
@@ -684,7 +737,7 @@ static int launch_integrate_plus_g(const MjhModel* m, const MjhData* d, int mode
   hipLaunchKernelGGL(k_integrate_plus<G>, dim3(nint + npub + nfac), dim3(256), lds, s, *m, *d, mode, nint, npub);
   return MJH_OK;
 }
-static int launch_integrate_plus(const MjhModel* m, const MjhData* d, int mode, bool integrate, hipStream_t s) { return launch_integrate_plus_g<32>(m, d, mode, integrate, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
+static int launch_integrate_plus(const MjhModel* m, const MjhData* d, int mode, bool integrate, bool with_factor, hipStream_t s) { return launch_integrate_plus_g<32>(m, d, mode, integrate, with_factor, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 // *sched_done: whether the launch carried the schedule workgroup (it needs >= 128 threads to be quick; otherwise it
 // rides with k_mid, whose workgroups always have 256)
 // control noise queued by mjh_timed_steps for the next fused step: it rides with that step's first launch
@@ -701,7 +754,7 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
   // whichever launch carried it -- fused k_fwd_pos 48 us against 39 us without it); with its loads in one batch (integrate.hpp schedule_body) it
   // costs this launch 2 us.  Same box, steady state / first steps, ms per step: here 0.2914 / 0.2698, as k_mid's last workgroup 0.2902 / 0.2745
   // (MJH_SCHED_IN_MID=1, developer knob).
-  static const bool sched_mid = mjh_knob("MJH_SCHED_IN_MID") != nullptr;
+  const bool sched_mid = KNOB_ONCE_FLAG("MJH_SCHED_IN_MID");
   *sched_done = threads >= 128 && !sched_mid;
   if (threads < 128) {
     if (noise.n) hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
@@ -715,7 +768,7 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
   hipLaunchKernelGGL(k_fwd_pos_plus<G>, dim3(npos + 1 + nnoise), dim3(threads), lds, s, *m, *d, first, last, npos, noise);
   return MJH_OK;
 }
-static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) { static const bool pos16 = mjh_knob("MJH_LANES16_POS") != nullptr; return lanes16(m) && pos16 ? launch_pos_plus_g<16>(m, d, first, last, sched_done, s) : lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, s) : launch_pos_plus_g<32>(m, d, first, last, sched_done, s); }
+static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) { const bool pos16 = KNOB_ONCE_FLAG("MJH_LANES16_POS"); return lanes16(m) && pos16 ? launch_pos_plus_g<16>(m, d, first, last, sched_done, s) : lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, s) : launch_pos_plus_g<32>(m, d, first, last, sched_done, s); }
 
 
 static int check(const MjhModel* m, const MjhData* d) {
@@ -768,7 +821,7 @@ struct Scope {
 };
 enum { K_NOISE = 0, K_POS = 1, K_COLLISION = 2, K_CONSTRAINT = 3, K_VEL = 4, K_SOLVE = 5, K_INTEGRATE = 6, K_OTHER = 7, K_MID = 8 };
 
-// Newton only: the public-output riders (contact publication, L'DL factor + qacc_smooth) cannot ride with the solver
+// Newton only (plan_step: RIDE_SIDE): the public-output riders (contact publication, L'DL factor + qacc_smooth) cannot ride with the solver
 // launch (its 256 VGPRs throttle them) and cost 55 us at the end of the integrator launch; they run on a low-priority
 // side stream beside the solver instead.  Two event hops (fork after k_mid, join after the integrator), neither on the
 // solver's critical path; created on first use per host thread and device, released by mjh_release_thread_resources().
@@ -780,8 +833,6 @@ struct Side {
 static thread_local Side* g_side_per_dev[16] = {nullptr};
 static Side* side_stream() {
   Side** per_dev = g_side_per_dev;
-  static const bool disabled = mjh_knob("MJH_NO_SIDE") != nullptr;  // developer knob
-  if (disabled) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   if (!per_dev[dev]) {
@@ -791,7 +842,7 @@ static Side* side_stream() {
     // developer knob (A/B): "high" / "normal"; default: the lowest priority.  Measured (round 3, two interleaved triples on one box): no
     // difference (0.2810 / 0.2803 / 0.2805 ms per Newton step) -- queue priority does not arbitrate CU slots.  The riders still end ~20 us
     // after the solver (rocprofv3 timeline, profiles/round3_newton_summary.json): their workgroups only get slots as the solver's retire
-    const char* pe = mjh_knob("MJH_SIDE_PRIO");
+    const char* pe = knob_str("MJH_SIDE_PRIO");
     const int prio = pe && pe[0] == 'h' ? greatest : (pe && pe[0] == 'n' ? 0 : least);
     // Round 6: the side stream IS the first auxiliary stream of the per-island solver (aux_streams; the two are never used by the same step).
     // A stream of its own cost every later model of the process its solver concurrency: once it existed -- any Newton model of at most 32
@@ -825,7 +876,7 @@ static int run_sleep_step(const MjhModel* m, const MjhData* d, bool step, hipStr
   if (!d->tree_asleep || !d->ws_sleep_J) return fail(MJH_E_ARG, "Data sleep tables missing (allocate Data with make_data/put_data)");
   if (m->solver != SOL_NEWTON) return fail(MJH_E_UNSUPPORTED, "sleeping requires the Newton solver (reference io.py:359)");
   if (step && m->integrator == INT_RK4) return fail(MJH_E_UNSUPPORTED, "sleeping with the RK4 integrator");
-  const int mode = m->integrator == INT_IMPLICITFAST ? 1 : (m->integrator == INT_IMPLICIT ? 2 : 0);
+  const int mode = integrator_mode(m);
   { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE, s)); }
   { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); }
   { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
@@ -953,11 +1004,12 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         TRY(run_stage(m, d, MJH_STAGE_FORWARD, s));
         return run_stage(m, d, MJH_STAGE_RUNGEKUTTA4, s);
       }
-      const int mode = m->integrator == INT_IMPLICITFAST ? 1 : (m->integrator == INT_IMPLICIT ? 2 : 0);
-      static const bool plain = mjh_knob("MJH_PLAIN") != nullptr;  // developer knob: one plain kernel per stage, serial
-      if ((g_instr && g_instr->on && g_instr->plain) || plain) {
+      const bool instrumented = g_instr && g_instr->on;
+      const bool plain = KNOB_ONCE_FLAG("MJH_PLAIN");  // developer knob: one plain kernel per stage, serial
+      if ((instrumented && g_instr->plain) || plain) {
         // profiling pass: one plain kernel per stage, so that the event pairs time one kernel at a time
-        { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, m->nv > 32 ? 64 : ((m->solver == SOL_NEWTON && m->cone == CONE_ELLIPTIC && d->njmax > 32) ? 32 : 0)); /* = sched_cls, integrate.hpp */ }
+        const int mode = integrator_mode(m);
+        { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, sched_cls_host(*m, *d)); }
         { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); }
         { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
         { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
@@ -971,11 +1023,10 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         TRY(launch_factor_smooth(m, d, m->solver == SOL_NEWTON ? 1 : 0, s));  // CG and PGS write qacc_smooth themselves
         return MJH_OK;
       }
-      // fused step: four launches on the caller's stream (see "composite launches" above)
-      // (nv <= 32 only: beside the 64-lane solver of larger models the riders cost more than they save, G1 -3 %)
-      static const int side_nv = mjh_knob("MJH_SIDE_NV") ? atoi(mjh_knob("MJH_SIDE_NV")) : 32;  // developer knob
-      const bool inl = stage == MJH_STAGE_STEP && newton_inline_ok(m, d) && !(g_instr && g_instr->on);
-      Side* side = (m->solver == SOL_NEWTON && m->nv <= side_nv && !(g_instr && g_instr->on) && !inl) ? side_stream() : nullptr;
+      // fused step: four launches on the caller's stream (see "composite launches" above), as plan_step decides
+      StepPlan p = plan_step(m, d, stage, instrumented);
+      Side* side = p.riders == RIDE_SIDE ? side_stream() : nullptr;
+      if (p.riders == RIDE_SIDE && !side) p = plan_step(m, d, stage, instrumented, false);  // (a failing device: the riders go with the integrator launch)
       bool sched_done = false;
       { Scope sc(K_POS); TRY(launch_pos_plus(m, d, POS_KINEMATICS, POS_CRB, &sched_done, s)); }
       { Scope sc(K_MID); TRY(launch_mid(m, d, !sched_done, s)); }
@@ -987,38 +1038,18 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         HIPCHK(hipStreamWaitEvent(side->stream, side->fork, 0));
         // both riders as roles of ONE launch (k_integrate_plus without integrator workgroups): their two chains overlap and one launch gap
         // goes (round 3, same-box A/B in two interleaved pairs: humanoid Newton 0.2842 -> 0.2829 / 0.2835 -> 0.2822 ms, Panda 142.9 -> 142.0 us)
-        static const bool side_two = mjh_knob("MJH_SIDE_TWO") != nullptr;  // developer knob (A/B): the two plain kernels of round 2
+        const bool side_two = KNOB_ONCE_FLAG("MJH_SIDE_TWO");  // developer knob (A/B): the two plain kernels of round 2
         if (!side_two) {
-          TRY(launch_integrate_plus(m, d, mode, false, side->stream));
+          TRY(launch_integrate_plus(m, d, p.mode, false, true, side->stream));
         } else {
           TRY(launch_publish(m, d, side->stream));
           TRY(launch_factor_smooth(m, d, 1, side->stream));
         }
         HIPCHK(hipEventRecord(side->join, side->stream));
       }
-      // explicit Euler without activations: the velocity/position update is a few loads and stores per dof, done by the
-      // solver's own epilogue (saves a launch); every other case keeps the integrator workgroups
-      // (Newton: only when its riders run on the side stream -- otherwise the integrator launch exists anyway, for them)
-      const bool fusable = stage == MJH_STAGE_STEP && m->na == 0 && (m->solver == SOL_CG || side != nullptr || inl) && m->nv <= 64 &&
-                           m->nsensor_acc == 0 &&  // (acceleration-stage sensors read qvel / qacc between the solver and the integrator)
-                           d->njmax <= 192;        // (beyond: some worlds go to the generic solver, which does not integrate)
-      // implicitfast without activations (round 3): the dense system (M + h D - h dA/dv) x = M qacc is solved from the M row the solver holds
-      static const bool no_fuse_impfast = mjh_knob("MJH_NO_FUSE_IMPLICITFAST") != nullptr;  // developer knob (A/B)
-      const int fuse_euler = !fusable ? 0
-                             : (m->integrator == INT_EULER && (m->disableflags & (DSBL_EULERDAMP | DSBL_DAMPER)) != 0) ? 1
-                             : (m->integrator == INT_IMPLICITFAST && !no_fuse_impfast && !m->act_velfeedback) ? 2 : 0;  // (positive velocity feedback: the matrix may be indefinite -- the integrator launch's L'DL handles that, the epilogue's Cholesky does not)
-      g_fuse_euler = fuse_euler;
-      g_newton_inline = inl;
-      int rc;
-      { Scope sc(K_SOLVE); rc = launch_solve_plus(m, d, s); }
-      g_fuse_euler = 0;
-      g_newton_inline = false;
-      TRY(rc);
+      { Scope sc(K_SOLVE); TRY(launch_solve_any(m, d, p, s)); }
       { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s)); }
-      g_riders_on_side = side != nullptr || inl;  // (either way the integrator launch carries no riders)
-      { Scope sc(K_INTEGRATE); rc = launch_integrate_plus(m, d, mode, stage == MJH_STAGE_STEP && !fuse_euler, s); }
-      g_riders_on_side = false;
-      TRY(rc);
+      { Scope sc(K_INTEGRATE); TRY(launch_integrate_plus(m, d, p.mode, stage == MJH_STAGE_STEP && !p.fuse_euler, p.riders == RIDE_INTEGRATOR, s)); }
       if (side) HIPCHK(hipStreamWaitEvent(s, side->join, 0));  // every fork rejoins the caller's stream
       return MJH_OK;
     }
@@ -1058,7 +1089,8 @@ int mjh_dev_knob(const char* name, const char* value) {
   if (!name || strncmp(name, "MJH_", 4) != 0) return fail(MJH_E_ARG, "mjh_dev_knob: knob names start with MJH_");
   KnobTable& t = knobs();
   std::lock_guard<std::mutex> lock(t.mu);
-  if (value) t.kv[name] = value;
+  if (t.latched.count(name)) return fail(MJH_E_ARG, "mjh_dev_knob: %s is latched (read once, at its first use, which has happened): set it in the environment before the library is loaded", name);
+  if (value) t.set(name, value);
   else t.kv.erase(name);
   t.n.store((int)t.kv.size(), std::memory_order_release);
   return MJH_OK;
@@ -1229,7 +1261,7 @@ int mjh_timed_steps(const MjhModel* m, const MjhData* d, int nstep, int step0, f
   for (int i = 0; i < nstep && rc == MJH_OK; ++i) {
     // the noise of step i rides with that step's first launch (the fused path); the per-kernel profiling passes and the plain
     // path keep it as its own kernel
-    static const bool plain_env = mjh_knob("MJH_PLAIN") != nullptr || mjh_knob("MJH_NO_NOISE_FUSION") != nullptr;
+    const bool plain_env = KNOB_ONCE_FLAG("MJH_PLAIN") || KNOB_ONCE_FLAG("MJH_NO_NOISE_FUSION");
     if (noise_std >= 0.0f && m->nu > 0) {
       if (instr.on || plain_env) rc = mjh_ctrl_noise(m, d, nullptr, step0 + i, noise_std, noise_rate, stream);
       else g_noise = NoiseArgs{d->nworld * m->nu, step0 + i, noise_std, noise_rate, nullptr, 0};
@@ -1263,17 +1295,7 @@ int mjh_timed_steps(const MjhModel* m, const MjhData* d, int nstep, int step0, f
   return MJH_OK;
 }
 
-#ifdef MJH_PHASE_CLOCK
-// profiling builds only (tools/phase_clock.py): read (and optionally reset) the per-kernel, per-phase tick sums
-int mjh_debug_phase_ticks(unsigned long long* out, int reset) {
-  if (out) HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_ticks), sizeof(unsigned long long) * 64 * 8 * 16));
-  if (reset) {
-    static unsigned long long zeros[64 * 8 * 16] = {0};
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zeros, sizeof(zeros)));
-  }
-  return MJH_OK;
-}
-#endif
-
 }  // extern "C"
 #pragma GCC visibility pop
+
+MJH_DEFINE_PHASE_TICKS  // (host.hpp)

@@ -29,9 +29,9 @@ static int launch_cgp_t(const MjhModel* m, const MjhData* d, bool with_factor, i
   // measured at 8192 humanoids, steady state / first steps: 64 threads 168.3 / 172.9 us, 128: 166.9 / 168.9, 192: 170.2 / 173.3; 384 and
   // 768 (an earlier build): 255 and 202 against 182 for 64
   int threads = 128;
-  if (const char* e = mjh_knob("MJH_CGP_THREADS")) threads = std::min(CGP_MAXT, std::max(64, (atoi(e) / 64) * 64));
+  if (const char* e = knob_str("MJH_CGP_THREADS")) threads = std::min(CGP_MAXT, std::max(64, (atoi(e) / 64) * 64));
   size_t lds = ((size_t)kLdsPerCU / (256 * CGP_WAVES / threads)) & ~(size_t)1023;  // (whole KB: the allocation granularity must not cost a workgroup)
-  if (const char* e = mjh_knob("MJH_CGP_LDS")) lds = (size_t)atoi(e);  // developer knob: bytes of the header + pool of a workgroup
+  if (const char* e = knob_str("MJH_CGP_LDS")) lds = (size_t)atoi(e);  // developer knob: bytes of the header + pool of a workgroup
   const int wpb = threads / 32;
   const int pool_rows = cgp_pool_rows<NV4>(lds, wpb);
   if (pool_rows < cgp_min_rows<NV4>(fuse_euler)) return fail(MJH_E_UNSUPPORTED, "k_solve_cgp: pool too small");
@@ -45,28 +45,7 @@ static int launch_cgp_t(const MjhModel* m, const MjhData* d, bool with_factor, i
   return MJH_OK;
 }
 int launch_solve_cgp(const MjhModel* m, const MjhData* d, bool with_factor, int fuse_euler, hipStream_t s) {
-  switch ((m->nv + 3) / 4) {
-    case 0:
-    case 1: return launch_cgp_t<1>(m, d, with_factor, fuse_euler, s);
-    case 2: return launch_cgp_t<2>(m, d, with_factor, fuse_euler, s);
-    case 3: return launch_cgp_t<3>(m, d, with_factor, fuse_euler, s);
-    case 4: return launch_cgp_t<4>(m, d, with_factor, fuse_euler, s);
-    case 5: return launch_cgp_t<5>(m, d, with_factor, fuse_euler, s);
-    case 6: return launch_cgp_t<6>(m, d, with_factor, fuse_euler, s);
-    case 7: return launch_cgp_t<7>(m, d, with_factor, fuse_euler, s);
-    default: return launch_cgp_t<8>(m, d, with_factor, fuse_euler, s);
-  }
+  return dispatch_nv4_32((m->nv + 3) / 4, [&](auto NV4) { return launch_cgp_t<NV4()>(m, d, with_factor, fuse_euler, s); });
 }
 
-#ifdef MJH_PHASE_CLOCK
-// profiling variant (tools/build_variant_fast.py clkp solve_cgp.hip -DMJH_PHASE_CLOCK; tools/phase_clock.py --lib ...): this unit's copy of the
-// per-phase tick sums of solve_cgp_body
-extern "C" __attribute__((visibility("default"))) int mjh_debug_phase_ticks(unsigned long long* out, int reset) {
-  if (out) HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_ticks), sizeof(unsigned long long) * 64 * 8 * 16));
-  if (reset) {
-    static unsigned long long zeros[64 * 8 * 16] = {0};
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zeros, sizeof(zeros)));
-  }
-  return MJH_OK;
-}
-#endif
+MJH_DEFINE_PHASE_TICKS  // (host.hpp)

@@ -29,7 +29,7 @@ static int launch_cgw_t(const MjhModel* m, const MjhData* d, bool with_factor, i
   size_t lds;
   int threads = pick_block(0, sizeof(float) * lay.total, 64, &lds, true);
   if (!threads) return fail(MJH_E_UNSUPPORTED, "k_solve_cgw: njmax x nv does not fit in LDS");
-  if (const char* e = mjh_knob("MJH_SOLVE_THREADS")) {  // tuning knob (developer only)
+  if (const char* e = knob_str("MJH_SOLVE_THREADS")) {  // tuning knob (developer only)
     threads = std::max(atoi(e), 64);
     lds = sizeof(float) * lay.total * (threads / 64);
   }
@@ -42,15 +42,5 @@ static int launch_cgw_t(const MjhModel* m, const MjhData* d, bool with_factor, i
   return MJH_OK;
 }
 int launch_solve_cgw(const MjhModel* m, const MjhData* d, bool with_factor, int fuse_euler, hipStream_t s, int lo, int hi) {
-  switch ((m->nv + 3) / 4) {
-    case 0:
-    case 1: return launch_cgw_t<1>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 2: return launch_cgw_t<2>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 3: return launch_cgw_t<3>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 4: return launch_cgw_t<4>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 5: return launch_cgw_t<5>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 6: return launch_cgw_t<6>(m, d, with_factor, fuse_euler, s, lo, hi);
-    case 7: return launch_cgw_t<7>(m, d, with_factor, fuse_euler, s, lo, hi);
-    default: return launch_cgw_t<8>(m, d, with_factor, fuse_euler, s, lo, hi);
-  }
+  return dispatch_nv4_32((m->nv + 3) / 4, [&](auto NV4) { return launch_cgw_t<NV4()>(m, d, with_factor, fuse_euler, s, lo, hi); });
 }

@@ -52,17 +52,7 @@ static int launch_tree_t(const MjhModel* m, const MjhData* d, hipStream_t s, int
 // (nv_lo, nv_hi]: dofs of the islands this launch solves; nv4 >= ceil(nv_hi / 4)
 template <int NR, bool NEWTON, bool LOOPED, bool ELL = false>
 static int launch_tree_32(const MjhModel* m, const MjhData* d, int nv4, hipStream_t s, int lo, int hi, int need, int nv_lo = 0, int nv_hi = 32) {
-  switch (nv4) {
-    case 0:
-    case 1: return launch_tree_t<1, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 2: return launch_tree_t<2, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 3: return launch_tree_t<3, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 4: return launch_tree_t<4, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 5: return launch_tree_t<5, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 6: return launch_tree_t<6, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    case 7: return launch_tree_t<7, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-    default: return launch_tree_t<8, NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need);
-  }
+  return dispatch_nv4_32(nv4, [&](auto NV4) { return launch_tree_t<NV4(), NR, NEWTON, 32, LOOPED, ELL>(m, d, s, lo, hi, nv_lo, nv_hi, need); });
 }
 // the two-size row dispatch of the whole-world solver (mjhip.hip launch_solve_any), per island.  `s`: the launch of the common class (islands
 // of at most 32 dofs and 64 rows); `sr`, `sr2`, `sr3`: the launches of the rare classes, which touch disjoint islands and run beside it (round 3:
@@ -77,7 +67,7 @@ static int launch_tree_all(const MjhModel* m, const MjhData* d, hipStream_t s, h
   // was solved with 32-wide rows of M / H and an 8-block Cholesky when the model also holds wide islands (clutter_synth: isl_nv4 = 8).
   // Models with small trees (the trees but the largest average at most 8 dofs) solve the islands of at most 8 / 16 dofs with the
   // instantiations of that size; the classes touch disjoint islands, so the wider ones go to the stream of the rare classes.
-  static const bool no_classes = mjh_knob("MJH_NO_ISLAND_CLASSES") != nullptr;  // developer knob (A/B)
+  const bool no_classes = KNOB_ONCE_FLAG("MJH_NO_ISLAND_CLASSES");  // developer knob (A/B)
   const int top4 = m->isl_nv4;
   const bool small = !no_classes && m->ntree > 1 && top4 > 2 && (m->nv - m->tree_nvmax) <= 8 * (m->ntree - 1);
   if (small) {

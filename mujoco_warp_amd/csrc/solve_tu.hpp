@@ -37,7 +37,7 @@ static int launch_solve_t(const MjhModel* m, const MjhData* d, bool with_factor,
   size_t lds;
   int threads = pick_block(0, sizeof(float) * lay.total, SG, &lds, true);
   if (!threads) return fail(MJH_E_UNSUPPORTED, "k_solve: njmax x nv does not fit in LDS");
-  if (const char* e = mjh_knob("MJH_SOLVE_THREADS")) {  // tuning knob (developer only)
+  if (const char* e = knob_str("MJH_SOLVE_THREADS")) {  // tuning knob (developer only)
     threads = std::max(atoi(e), SG);
     lds = sizeof(float) * lay.total * (threads / SG);
   }
@@ -51,7 +51,7 @@ static int launch_solve_t(const MjhModel* m, const MjhData* d, bool with_factor,
   // where the riders sit in the dispatch order, in per cent of the solver workgroups (developer knob; 100 = after all of them, the round-1 layout).
   // Measured (round 3, humanoid CG, two interleaved rounds on one box): 100 -> 215.9 / 215.3 us per launch, 75 -> 280.4 / 280.7, 55 -> 268.6 / 267.6,
   // 35 -> 279.1 / 279.0: riders dispatched among the solver workgroups cost four times what they cost in the launch's tail
-  static const int rider_pct = mjh_knob("MJH_RIDER_AT") ? atoi(mjh_knob("MJH_RIDER_AT")) : 100;
+  const int rider_pct = KNOB_ONCE_INT("MJH_RIDER_AT", 100);
   const int rider_at = std::min(nsolve, (int)((long long)nsolve * std::max(rider_pct, 0) / 100));
   hipLaunchKernelGGL((k_solve_plus<NV4, NR, NEWTON, SG, ELL>), dim3(nsolve + 2 * nfac), dim3(threads), lds, s, *m, *d, nsolve, nfac, nefc_lo, nefc_hi, fuse_euler, rider_at);
   return MJH_OK;
@@ -88,24 +88,9 @@ static int launch_solve_deferred_t(const MjhModel* m, const MjhData* d, int fuse
 }
 template <int NR, bool NEWTON, bool ELL = false>
 static int launch_solve_32(const MjhModel* m, const MjhData* d, bool wf, int fe, hipStream_t s, int lo, int hi) {
-  switch ((m->nv + 3) / 4) {  // kernels are specialised on ceil(nv/4): no padded matrix columns
-    case 0:
-    case 1: return launch_solve_t<1, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 2: return launch_solve_t<2, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 3: return launch_solve_t<3, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 4: return launch_solve_t<4, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 5: return launch_solve_t<5, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 6: return launch_solve_t<6, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    case 7: return launch_solve_t<7, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-    default: return launch_solve_t<8, NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi);
-  }
+  return dispatch_nv4_32((m->nv + 3) / 4, [&](auto NV4) { return launch_solve_t<NV4(), NR, NEWTON, 32, ELL>(m, d, wf, fe, s, lo, hi); });
 }
 template <int NR, bool NEWTON, bool ELL = false>
 static int launch_solve_64(const MjhModel* m, const MjhData* d, bool wf, int fe, hipStream_t s, int lo, int hi) {
-  const int nv4 = (m->nv + 3) / 4;  // rounded up to an instantiated size (lanes past nv hold identity rows)
-  if (nv4 <= 9) return launch_solve_t<9, NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi);
-  if (nv4 <= 10) return launch_solve_t<10, NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi);
-  if (nv4 <= 12) return launch_solve_t<12, NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi);
-  if (nv4 <= 14) return launch_solve_t<14, NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi);
-  return launch_solve_t<16, NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi);
+  return dispatch_nv4_64((m->nv + 3) / 4, [&](auto NV4) { return launch_solve_t<NV4(), NR, NEWTON, 64, ELL>(m, d, wf, fe, s, lo, hi); });
 }

@@ -562,3 +562,48 @@ def test_cull_tables_edge_cases():
   x = pos[:7]
   want = int(np.argmin((np.linalg.norm(x[:, None] - x[None], axis=2) + 0.1).max(axis=1)))
   assert group[0, 0] == want and (cgeom[:7, 1] == want).all()
+
+
+_CSRC = os.path.join(os.path.dirname(_abi.__file__), "csrc")
+
+
+def _csrc_text():
+  return {f: open(os.path.join(_CSRC, f)).read() for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))}
+
+
+def test_unity_build_lists_every_unit():
+  """csrc/unity.hip (the one-command developer build) includes exactly the translation units the product builder compiles, in its order."""
+  inc = re.findall(r'^#include "([^"]+\.hip)"', open(os.path.join(_CSRC, "unity.hip")).read(), flags=re.M)
+  assert inc == _abi.UNITS
+
+
+def test_knob_table_in_design_md_matches_the_code():
+  """Every "MJH_*" string literal under csrc/ is a developer knob and is listed once in the table of DESIGN.md section 3.1, and the other way round."""
+  used = set()
+  for text in _csrc_text().values():
+    used |= set(re.findall(r'"(MJH_[A-Z0-9_]+)"', text))
+  design = open(os.path.join(conftest.ROOT, "DESIGN.md")).read()
+  rows = re.findall(r"^\| `(MJH_[A-Z0-9_]+)` \| [^|]+ \| (live|latched) \|", design, flags=re.M)
+  assert len(rows) == len(set(n for n, _ in rows)), "a knob is listed twice"
+  assert set(n for n, _ in rows) == used
+  assert "MJH_LIB" not in used  # (the loader's variable, _abi.py: not a library knob)
+
+
+def test_launch_decisions_travel_in_the_plan_not_in_globals():
+  """The step plan is passed down explicitly (no thread-local side channels), and the ceil(nv / 4) ladder exists once per lane count (host.hpp)."""
+  text = _csrc_text()
+  for f, t in text.items():
+    assert not re.search(r"g_fuse_euler|g_newton_inline|g_riders_on_side", t), f
+    assert not re.search(r"mjh_knob\(\"", t), f"{f}: a bare mjh_knob(\"...\") read; use knob_* (live) or KNOB_ONCE_* (latched)"
+  ladders = sum(len(re.findall(r"switch \(\(m->nv \+ 3\) / 4\)|switch \(nv4\)|if \(nv4 <= 9\)", t)) for t in text.values())
+  assert ladders <= 2, ladders
+
+
+def test_dev_knobs_refuses_to_shadow_an_environment_value(monkeypatch):
+  """A knob that came from the environment snapshot cannot be read back (no getter in the ABI), so dev_knobs raises instead of losing it."""
+  monkeypatch.setattr(_abi, "_env_knobs", {"MJH_CG_KERNEL"})
+  monkeypatch.setattr(_abi, "_knob_values", {})
+  monkeypatch.setattr(_abi, "lib", lambda: None)
+  with pytest.raises(_abi.EngineError, match="MJH_CG_KERNEL"):
+    with _abi.dev_knobs(MJH_CG_KERNEL="pair"):
+      pass

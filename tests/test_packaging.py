@@ -130,3 +130,39 @@ def test_dev_knob_hook_replaces_the_environment():
   assert mjw.solver_kernel(m, d) == "cgp"
   with pytest.raises(_abi.EngineError):
     _abi.set_knob("NOT_A_KNOB", "1")
+
+
+@pytest.mark.gpu
+def test_solver_kernel_names_the_kernel_of_a_fused_implicitfast_step():
+  """The one-world-per-wavefront CG kernel cannot serve the fused implicitfast update (its half rows of M), so a small implicitfast batch runs
+  the pooled kernel: solver_kernel reports the plan the step launches, not a restatement of it."""
+  import mujoco_warp_amd as mjw
+
+  mjm = mjw.mjcf.load_xml(conftest.HUMANOID_XML)
+  mjm.opt.solver = int(mjw.SolverType.CG)
+  assert mjw.solver_kernel(mjw.put_model(mjm), mjw.make_data(mjm, nworld=1024, nconmax=24, njmax=64)) == "cgw"  # Euler
+  mjm.opt.integrator = int(mjw.IntegratorType.IMPLICITFAST)
+  m = mjw.put_model(mjm)
+  assert m.cg_basis and not m.act_velfeedback
+  assert mjw.solver_kernel(m, mjw.make_data(mjm, nworld=1024, nconmax=24, njmax=64)) == "cgp"
+
+
+@pytest.mark.gpu
+def test_dev_knobs_restore_and_latched_knobs_refuse():
+  """Nested dev_knobs blocks unwind to the enclosing block's value; a latched knob (read once at first use) cannot be set afterwards."""
+  import mujoco_warp_amd as mjw
+  from mujoco_warp_amd import _abi
+
+  mjm = mjw.mjcf.load_xml(conftest.HUMANOID_XML)
+  mjm.opt.solver = int(mjw.SolverType.CG)
+  m = mjw.put_model(mjm)
+  d = mjw.make_data(mjm, nworld=8192, nconmax=24, njmax=64)
+  with _abi.dev_knobs(MJH_CG_KERNEL="cgw"):
+    assert mjw.solver_kernel(m, d) == "cgw"
+    with _abi.dev_knobs(MJH_CG_KERNEL="pair"):
+      assert mjw.solver_kernel(m, d) == "pair"
+    assert mjw.solver_kernel(m, d) == "cgw"
+  assert mjw.solver_kernel(m, d) == "cgp"
+  # MJH_CGW_MIN_NV is latched by the plan of the calls above
+  with pytest.raises(_abi.EngineError, match="MJH_CGW_MIN_NV"):
+    _abi.set_knob("MJH_CGW_MIN_NV", 1)

@@ -106,8 +106,51 @@ def pmc(dbpath):
     ndisp[k].add(ev)
   return {k: {c: v / max(len(ndisp[k]), 1) for c, v in cs.items()} for k, cs in per.items()}
 
+# solver family (mjh_solver_kernel / mjw.solver_kernel) -> the solver kernel a trace of that family must hold (as its mangled name spells
+# it, length prefix included: "11k_solve_pgs" is not part of "15k_solve_pgs_big")
+_PLUS, _CGP, _CGW, _MFMA = "12k_solve_plus", "16k_solve_cgp_plus", "16k_solve_cgw_plus", "14k_solve_newton"
+FAMILY_KERNELS = {"cgp": _CGP, "cgw": _CGW, "newton_mfma": _MFMA, "pair": _PLUS, "cg32_ell": _PLUS, "newton32": _PLUS, "newton32_ell": _PLUS, "cg64": _PLUS,
+                  "cg64_ell": _PLUS, "newton64": _PLUS, "newton64_ell": _PLUS, "pgs": "11k_solve_pgs", "pgs_big": "15k_solve_pgs_big", "big": "11k_solve_big",
+                  "tree+big": "12k_solve_tree"}
+
+
+def launch_shapes(dbpath):
+  """{(full kernel name, grid x, workgroup x, LDS bytes): calls} of a kernel trace: what a host-only change must leave exactly as it was
+  (compare the --shapes listings of two builds with diff)."""
+  db = sqlite3.connect(dbpath)
+  cur = db.cursor()
+  t = _tables(cur)
+  names = {r[0]: r[1] for r in cur.execute(f"select id, kernel_name from '{t['rocpd_info_kernel_symbol']}'")}
+  cols = [r[1] for r in cur.execute(f"pragma table_info('{t['rocpd_kernel_dispatch']}')")]
+  pick = lambda *c: next(x for x in c if x in cols)
+  q = f"select kernel_id, {pick('grid_size_x', 'grid_x')}, {pick('workgroup_size_x', 'workgroup_x')}, {pick('group_segment_size', 'lds_block_size', 'lds_size')} from '{t['rocpd_kernel_dispatch']}'"
+  out = defaultdict(int)
+  for kid, g, w, lds in cur.execute(q):
+    out[(names.get(kid, str(kid)).replace(".kd", ""), g, w, lds)] += 1
+  return dict(out)
+
+
+def family_consistent(shapes, family):
+  """The family string names the solver kernel that ran: its kernel is in the trace, and cgp / cgw / the MFMA kernel are not there unless named."""
+  ran = {k for k in set(FAMILY_KERNELS.values()) if any(k in name for name, *_ in shapes)}
+  return FAMILY_KERNELS[family] in ran and not (ran & {_CGP, _CGW, _MFMA}) - {FAMILY_KERNELS[family]}
+
+
+def main_shapes(argv):
+  """summarize_profile.py --shapes <trace.db> [family]: one line per (kernel, grid, workgroup, LDS) with its call count, sorted."""
+  shapes = launch_shapes(argv[0])
+  for (name, g, w, lds), n in sorted(shapes.items()):
+    print(f"{n:6d} x grid {g:8d} workgroup {w:4d} lds {lds:7d}  {name}")
+  if len(argv) > 1:
+    ok = family_consistent(shapes, argv[1])
+    print(f"solver_kernel {argv[1]}: {'consistent with' if ok else 'NOT CONSISTENT WITH'} the solver kernels of the trace")
+    return 0 if ok else 1
+  return 0
+
 
 def main():
+  if sys.argv[1] == "--shapes":
+    sys.exit(main_shapes(sys.argv[2:]))
   out = sys.argv[1]
   summary = {"source": out}
   for f in glob.glob(os.path.join(out, "trace", "*.db")):

@@ -1,5 +1,7 @@
 #!/bin/bash
 # GPU box: kernel trace of one registry benchmark (benchmarks/run.py -f <name>): which kernels take the time.  usage: tools/trace_run.sh <filter> [nstep]
+# TRACE_SHAPES=<file>: also write the launch shapes (kernel, grid, workgroup, LDS, calls: tools/summarize_profile.py --shapes) there -- run it
+# with MJH_LIB=<other build> and diff the two files to show that a host-only change left every launch as it was
 OUT=$PWD/gpurun_out/prof_run_$1
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
@@ -13,4 +15,5 @@ for f in glob.glob(os.path.join(sys.argv[1], "trace", "*.db")):
   for k in sp.kernel_trace(f)[:18]:
     print(f"{k['kernel'][:40]:40s} calls {k['calls']:5d} mean {k['mean_us']:8.1f} us  {k['pct']:5.1f} %")
 PY
+if [ -n "$TRACE_SHAPES" ]; then for f in $OUT/trace/*.db; do python tools/summarize_profile.py --shapes $f; done > "$TRACE_SHAPES"; fi
 rm -rf $OUT/trace
