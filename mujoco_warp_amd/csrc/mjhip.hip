@@ -109,6 +109,18 @@ int pick_block(size_t shared_bytes, size_t per_world_bytes, int G, size_t* lds_o
   if (best) *lds_out = shared_bytes + per_world_bytes * (best / G);
   return best;
 }
+// The launch of a plain "one lane group per world" kernel: the workgroup pick_block chooses for its LDS needs (shared_bytes per workgroup +
+// per_world_bytes per world), threads / G worlds per workgroup.  unfit: the message when not even the smallest workgroup fits in LDS.
+template <typename K, typename... Args>
+static int launch_per_world(K kernel, const char* unfit, int G, size_t shared_bytes, size_t per_world_bytes, int nworld, hipStream_t s, const Args&... args) {
+  size_t lds;
+  const int threads = pick_block(shared_bytes, per_world_bytes, G, &lds);
+  if (!threads) return fail(MJH_E_UNSUPPORTED, unfit);
+  HIPCHK(set_lds(kernel, lds));
+  const int wpb = threads / G;
+  hipLaunchKernelGGL(kernel, dim3((nworld + wpb - 1) / wpb), dim3(threads), lds, s, args...);
+  return MJH_OK;
+}
 
 // Lanes per world of every kernel but the solvers (which choose their own): 32 -- two worlds per wavefront -- for models of at most 32 dofs
 // and bodies, 64 beyond (round 3): these kernels are chains of dependent steps whose loops stride over dofs / bodies / geoms by the
@@ -121,53 +133,35 @@ static inline bool lanes64(const MjhModel* m) {
 }
 // 16 lanes per world -- four worlds per wavefront -- in k_mid for small models (at most 16 dofs and bodies, light colliders; round 3): half the
 // wavefronts for the same worlds and still one trip per loop.  Same-box A/B: Panda 8192 worlds k_mid 62.0 -> 49.5 us, step 180 -> 164.6 us
-// (- 8.7 %).  Not for larger models (humanoid, 27 dofs on 17 bodies, forced with MJH_LANES16_ANY: k_mid 84 -> 101 us -- every loop needs two
-// trips) and not for k_fwd_pos (Panda 48.0 vs 49.1 us: its chain is the tree depth whatever the lane count; MJH_LANES16_POS turns it on).
+// (- 8.7 %).  Not for larger models (forced on the humanoid, 27 dofs on 17 bodies: k_mid 84 -> 101 us -- every loop needs two trips) and not
+// for k_fwd_pos (Panda 48.0 vs 49.1 us: its chain is the tree depth whatever the lane count): both experiments lost, their knobs are retired.
 static inline bool lanes16(const MjhModel* m) {
-  const int force = KNOB_ONCE_INT("MJH_LANES", 0);  // developer knob: 16 / 32 / 64
-  const bool any = KNOB_ONCE_FLAG("MJH_LANES16_ANY");
+  const int force = KNOB_ONCE_INT("MJH_LANES", 0);  // developer knob: 32 / 64 forbid it; 16 is the default's choice, never beyond 16 dofs / bodies
   if (force && force != 16) return false;
-  return ((m->nv <= 16 && m->nbody <= 16) || (force == 16 && any)) && !m->heavy_colliders;
+  return m->nv <= 16 && m->nbody <= 16 && !m->heavy_colliders;
 }
 // (k_fwd_pos: its loops run over bodies -- the G1, 35 dofs on 30 bodies, is 4 us slower with 64 lanes; three humanoids, 52 bodies, 25 us faster)
 
 template <int G>
 static int launch_pos_g(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) {
   const PosLayout lay = pos_layout(m->nq, m->nv, m->nbody, m->njnt, m->nC, last >= POS_FACTOR);
-  size_t lds;
-  const int threads = pick_block(sizeof(int) * pos_shared_words(m->nv, m->nC, m->nbody, m->njnt, m->nbodylevel, m->ngeom, m->nsite), sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_fwd_pos: model does not fit in LDS");
-  HIPCHK(set_lds(k_fwd_pos<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_fwd_pos<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d, first, last);
-  return MJH_OK;
+  return launch_per_world(k_fwd_pos<G>, "k_fwd_pos: model does not fit in LDS", G, sizeof(int) * pos_shared_words(m->nv, m->nC, m->nbody, m->njnt, m->nbodylevel, m->ngeom, m->nsite),
+                          sizeof(float) * lay.total, d->nworld, s, *m, *d, first, last);
 }
 static int launch_pos(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) { return lanes64(m) && m->nbody > 32 ? launch_pos_g<64>(m, d, first, last, s) : launch_pos_g<32>(m, d, first, last, s); }
 template <int G>
 static int launch_vel_g(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) {
   const VelLayout lay = vel_layout(m->nq, m->nv, m->nbody, m->nC, m->nu);
-  size_t lds;
-  const int threads = pick_block(sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_fwd_vel: model does not fit in LDS");
-  HIPCHK(set_lds(k_fwd_vel<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_fwd_vel<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d, first, last);
-  return MJH_OK;
+  return launch_per_world(k_fwd_vel<G>, "k_fwd_vel: model does not fit in LDS", G, sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, d->nworld, s, *m, *d, first, last);
 }
 static int launch_vel(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) { return lanes64(m) ? launch_vel_g<64>(m, d, first, last, s) : launch_vel_g<32>(m, d, first, last, s); }
 // public L'DL factor (qLD, qLDiagInv) and, on request, qacc_smooth: outputs nobody inside the step waits for
-template <int G>
-static int launch_factor_smooth_g(const MjhModel* m, const MjhData* d, int write_qacc, hipStream_t s) {
+// (32 lanes per world here and in the other kernels that chain over the sparse factor -- k_integrate, k_integrate_plus, k_solve_m, and
+// k_publish_contacts with them: more lanes per world only halve the worlds per wavefront)
+static int launch_factor_smooth(const MjhModel* m, const MjhData* d, int write_qacc, hipStream_t s) {
   const FacLayout lay = fac_layout(m->nv, m->nC);
-  size_t lds;
-  const int threads = pick_block(sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_factor_smooth: model does not fit in LDS");
-  HIPCHK(set_lds(k_factor_smooth<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_factor_smooth<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d, write_qacc);
-  return MJH_OK;
+  return launch_per_world(k_factor_smooth<32>, "k_factor_smooth: model does not fit in LDS", 32, sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, d->nworld, s, *m, *d, write_qacc);
 }
-static int launch_factor_smooth(const MjhModel* m, const MjhData* d, int write_qacc, hipStream_t s) { return launch_factor_smooth_g<32>(m, d, write_qacc, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 // the three launches of the convex narrowphase in front of a contact kernel (models with GJK pairs; csrc/convex.hpp header)
 template <int G>
 static int launch_ccd_pre(const MjhModel* m, const MjhData* d, hipStream_t s) {
@@ -182,12 +176,8 @@ static int launch_ccd_pre(const MjhModel* m, const MjhData* d, hipStream_t s) {
     hipLaunchKernelGGL(k_broad_mask, dim3((unsigned)std::min(d->nworld, 8192)), dim3(256), lds_mask, s, *m, *d);
   }
   if (m->broadphase != 0 || m->npair == 0) {  // sweep-and-prune: the broadphase of a world by its lane group (k_broad_mask publishes the NXN list itself)
-    size_t lds;
-    const int threads = pick_block(sizeof(float) * 9 * m->ngeom, sizeof(float) * broad_lds_words(m->ngeom, m->npair, d->concap, m->broadphase), G, &lds);  // (+ the staged model tables)
-    if (!threads) return fail(MJH_E_UNSUPPORTED, "k_ccd_broad: pair list does not fit in LDS");
-    HIPCHK(set_lds((k_ccd_broad<G>), lds));
-    const int wpb = threads / G;
-    hipLaunchKernelGGL((k_ccd_broad<G>), dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d);
+    TRY(launch_per_world(k_ccd_broad<G>, "k_ccd_broad: pair list does not fit in LDS", G, sizeof(float) * 9 * m->ngeom,  // (the staged model tables)
+                         sizeof(float) * broad_lds_words(m->ngeom, m->npair, d->concap, m->broadphase), d->nworld, s, *m, *d));
   }
   // (grids sized for the device -- 256 CUs x 8 workgroups --, not for the lists' capacities: the kernels walk their lists with the grid's stride)
   {
@@ -216,47 +206,22 @@ static int launch_ccd_pre(const MjhModel* m, const MjhData* d, hipStream_t s) {
 }
 template <int G>
 static int launch_collision_g(const MjhModel* m, const MjhData* d, hipStream_t s) {
-  if (m->heavy_colliders && d->ws_ccd) {
-    const int rc = launch_ccd_pre<G>(m, d, s);
-    if (rc != MJH_OK) return rc;
-  }
-  size_t lds;
-  const int threads = pick_block(0, sizeof(float) * collide_lds_words(m->ngeom, m->npair, d->concap, m->heavy_colliders ? m->broadphase : 0, m->heavy_colliders && d->ws_ccd != nullptr), G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_collision: pair list does not fit in LDS");
-  if (m->heavy_colliders) {
-    const int wpb_h = threads / G;
-    if (m->nhfield > 0) {
-      HIPCHK(set_lds((k_collision<G, true, true>), lds));
-      hipLaunchKernelGGL((k_collision<G, true, true>), dim3((d->nworld + wpb_h - 1) / wpb_h), dim3(threads), lds, s, *m, *d);
-    } else {  // (without the height-field colliders: the registers of their per-lane GJK / EPA)
-      HIPCHK(set_lds((k_collision<G, true, false>), lds));
-      hipLaunchKernelGGL((k_collision<G, true, false>), dim3((d->nworld + wpb_h - 1) / wpb_h), dim3(threads), lds, s, *m, *d);
-    }
-    return MJH_OK;
-  }
-  HIPCHK(set_lds((k_collision<G, false>), lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL((k_collision<G, false>), dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d);
-  return MJH_OK;
+  if (m->heavy_colliders && d->ws_ccd) TRY(launch_ccd_pre<G>(m, d, s));
+  const size_t per_world = sizeof(float) * collide_lds_words(m->ngeom, m->npair, d->concap, m->heavy_colliders ? m->broadphase : 0, m->heavy_colliders && d->ws_ccd != nullptr);
+  auto go = [&](auto kernel) { return launch_per_world(kernel, "k_collision: pair list does not fit in LDS", G, 0, per_world, d->nworld, s, *m, *d); };
+  if (!m->heavy_colliders) return go(k_collision<G, false>);
+  return m->nhfield > 0 ? go(k_collision<G, true, true>) : go(k_collision<G, true, false>);  // (without the height-field colliders: the registers of their per-lane GJK / EPA)
 }
 static int launch_collision(const MjhModel* m, const MjhData* d, hipStream_t s) { return lanes64(m) ? launch_collision_g<64>(m, d, s) : launch_collision_g<32>(m, d, s); }
 // compact public contact arrays, contact.efc_address and efc.id of contact rows from the per-world records
-template <int G>
-static int launch_publish_g(const MjhModel* m, const MjhData* d, hipStream_t s) {
-  hipLaunchKernelGGL(k_publish_contacts<G>, dim3((d->nworld + 256 / G - 1) / (256 / G)), dim3(256), 0, s, *d, 1, m->nexplicit ? m->pair_solreffriction : nullptr);
+static int launch_publish(const MjhModel* m, const MjhData* d, hipStream_t s) {
+  hipLaunchKernelGGL(k_publish_contacts<32>, dim3((d->nworld + 256 / 32 - 1) / (256 / 32)), dim3(256), 0, s, *d, 1, m->nexplicit ? m->pair_solreffriction : nullptr);
   return MJH_OK;
 }
-static int launch_publish(const MjhModel* m, const MjhData* d, hipStream_t s) { return launch_publish_g<32>(m, d, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 template <int G>
 static int launch_constraint_g(const MjhModel* m, const MjhData* d, hipStream_t s) {
   const ConLayout lay = con_layout(m->nv, d->njmax, d->concap, m->nbody, m->ngeom);
-  size_t lds;
-  const int threads = pick_block(0, sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_make_constraint: does not fit in LDS");
-  HIPCHK(set_lds(k_make_constraint<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_make_constraint<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d);
-  return MJH_OK;
+  return launch_per_world(k_make_constraint<G>, "k_make_constraint: does not fit in LDS", G, 0, sizeof(float) * lay.total, d->nworld, s, *m, *d);
 }
 static int launch_constraint(const MjhModel* m, const MjhData* d, hipStream_t s) { return lanes64(m) ? launch_constraint_g<64>(m, d, s) : launch_constraint_g<32>(m, d, s); }
 static int launch_rne_postconstraint(const MjhModel* m, const MjhData* d, hipStream_t s) {
@@ -305,19 +270,11 @@ static int launch_implicit(const MjhModel* m, const MjhData* d, hipStream_t s) {
   hipLaunchKernelGGL(k_implicit_solve<32>, dim3((d->nworld + wpb - 1) / wpb), dim3(32 * wpb), lds, s, *m, *d);
   return MJH_OK;
 }
-template <int G>
-static int launch_integrate_g(const MjhModel* m, const MjhData* d, int mode, hipStream_t s) {
+static int launch_integrate(const MjhModel* m, const MjhData* d, int mode, hipStream_t s) {
   if (mode == 2) TRY(launch_implicit(m, d, s));
   const IntLayout lay = int_layout(m->nv, m->nC);
-  size_t lds;
-  const int threads = pick_block(sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_integrate: does not fit in LDS");
-  HIPCHK(set_lds(k_integrate<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_integrate<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d, mode);
-  return MJH_OK;
+  return launch_per_world(k_integrate<32>, "k_integrate: does not fit in LDS", 32, sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, d->nworld, s, *m, *d, mode);
 }
-static int launch_integrate(const MjhModel* m, const MjhData* d, int mode, hipStream_t s) { return launch_integrate_g<32>(m, d, mode, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 
 // ---- composite launches of the fused step --------------------------------------------------------------------
 // Cross-stream fork/join costs 5-15 us per hop on the critical path (event record -> barrier packet -> dispatch),
@@ -384,11 +341,8 @@ __global__ void __launch_bounds__(256) k_fwd_pos_plus(MjhModel m, MjhData d, int
 
 template <int G>
 static int launch_mid_g(const MjhModel* m, const MjhData* d, bool sched, hipStream_t s) {
-  if constexpr (G != 16) {
-    if (m->heavy_colliders && d->ws_ccd) {
-      const int rc = launch_ccd_pre<G>(m, d, s);
-      if (rc != MJH_OK) return rc;
-    }
+  if constexpr (G != 16) {  // (16 lanes: light colliders only, see lanes16)
+    if (m->heavy_colliders && d->ws_ccd) TRY(launch_ccd_pre<G>(m, d, s));
   }
   const ConLayout cl = con_layout(m->nv, d->njmax, d->concap, m->nbody, m->ngeom);
   const int stride_cc = std::max(cl.total, collide_lds_words(m->ngeom, m->npair, d->concap, m->heavy_colliders ? m->broadphase : 0, m->heavy_colliders && d->ws_ccd != nullptr) | 1);
@@ -414,26 +368,18 @@ static int launch_mid_g(const MjhModel* m, const MjhData* d, bool sched, hipStre
   }
   lds = std::max(lds, ms_bytes + sizeof(float) * vl.total * nw_v);
   if (lds > (size_t)kLdsPerCU) return fail(MJH_E_UNSUPPORTED, "k_mid: model does not fit in LDS");
-  if constexpr (G == 16) {  // (light colliders only: lanes16)
-    HIPCHK(set_lds((k_mid<G, false>), lds));
-    const int ncc16 = (d->nworld + nw_cc - 1) / nw_cc, nvb16 = (d->nworld + nw_v - 1) / nw_v;
-    hipLaunchKernelGGL((k_mid<G, false>), dim3(ncc16 + nvb16 + (sched ? 1 : 0)), dim3(G * std::max(nw_cc, nw_v)), lds, s, *m, *d, ncc16, nvb16, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
-    return MJH_OK;
-  } else {
-  const bool hf = m->nhfield > 0;  // (heavy colliders without height fields: the instantiation without their per-lane GJK / EPA)
-  if (m->heavy_colliders && hf) HIPCHK(set_lds((k_mid<G, true, true>), lds));
-  else if (m->heavy_colliders) HIPCHK(set_lds((k_mid<G, true, false>), lds));
-  else HIPCHK(set_lds((k_mid<G, false>), lds));
   const int ncc = (d->nworld + nw_cc - 1) / nw_cc, nvb = (d->nworld + nw_v - 1) / nw_v;
   const dim3 grid(ncc + nvb + (sched ? 1 : 0)), block(G * std::max(nw_cc, nw_v));
-  if (m->heavy_colliders && hf) debug_occupancy("k_mid<heavy>", k_mid<G, true, true>, (int)grid.x, (int)block.x, lds);
-  else if (m->heavy_colliders) debug_occupancy("k_mid<heavy>", k_mid<G, true, false>, (int)grid.x, (int)block.x, lds);
-  else debug_occupancy("k_mid", k_mid<G, false>, (int)grid.x, (int)block.x, lds);
-  if (m->heavy_colliders && hf) hipLaunchKernelGGL((k_mid<G, true, true>), grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
-  else if (m->heavy_colliders) hipLaunchKernelGGL((k_mid<G, true, false>), grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
-  else hipLaunchKernelGGL((k_mid<G, false>), grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
-  return MJH_OK;
+  auto go = [&](auto kernel, const char* name) {
+    HIPCHK(set_lds(kernel, lds));
+    debug_occupancy(name, kernel, (int)grid.x, (int)block.x, lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, *m, *d, ncc, nvb, nw_cc, nw_v, stride_cc, sched ? 1 : 0);
+    return MJH_OK;
+  };
+  if constexpr (G != 16) {  // (heavy colliders without height fields: the instantiation without their per-lane GJK / EPA)
+    if (m->heavy_colliders) return m->nhfield > 0 ? go(k_mid<G, true, true>, "k_mid<heavy>") : go(k_mid<G, true, false>, "k_mid<heavy>");
   }
+  return go(k_mid<G, false>, "k_mid");
 }
 static int launch_mid(const MjhModel* m, const MjhData* d, bool sched, hipStream_t s) { return lanes16(m) ? launch_mid_g<16>(m, d, sched, s) : lanes64(m) ? launch_mid_g<64>(m, d, sched, s) : launch_mid_g<32>(m, d, sched, s); }
 static int solve_supported(const MjhModel* m, const MjhData* d) {
@@ -574,58 +520,6 @@ static StepPlan plan_step(const MjhModel* m, const MjhData* d, int stage, bool i
   p.r1 = p.family == FAM_NEWTON32_ELL && d->njmax > 32 && KNOB_ONCE_INT("MJH_SOLVE_R1", 1) != 0;
   return p;
 }
-#ifndef MJH_SOLVE64_SPLIT_DEFAULT
-#define MJH_SOLVE64_SPLIT_DEFAULT 0
-#endif
-// the launches of the 64-lane families (32 < nv <= 64): k_solve_plus by rows per lane
-static int launch_solve_rows_64(const MjhModel* m, const MjhData* d, const StepPlan& p, hipStream_t s) {
-  const int fe = p.fuse_euler, all = 0x7fffffff, top = d->njmax > 192 ? 192 : all;  // (top: see launch_solve_any)
-  const bool with_factor = p.riders == RIDE_SOLVER;
-  auto s64 = p.ell ? (p.newton ? launch_solve_64_newton_ell : launch_solve_64_cg_ell) : (p.newton ? launch_solve_64_newton : launch_solve_64_cg);
-  // 64 lanes per world: 1 / 2 / 3 rows per lane cover 64 / 128 / 192 rows.  The second launch of a pair runs after the
-  // first on the same stream, so the split point is chosen to leave it (almost) empty: its real worlds would otherwise
-  // be a serial tail on an idle GPU (G1: 6 % of the worlds exceed 64 rows, practically none exceed 128)
-  if (d->njmax <= 64) return s64(m, d, 1, with_factor, fe, s, -1, all);
-  // (developer knob MJH_SOLVE64_R1=1: the worlds of at most 64 rows by the one-row instantiation -- half the J tile -- in a launch of their own.
-  // Measured on the G1 replay, 4096 worlds, nefc 68 on average: bit-identical states, 7.84 vs 9.14 M env-steps/s -- a second launch with real
-  // worlds costs the latency of one more solve.  Off.)
-  const bool r1_64 = KNOB_ONCE_INT("MJH_SOLVE64_R1", 0) != 0;
-  int lo64 = -1;
-  if (r1_64) {
-    if (int rc = s64(m, d, 1, false, fe, s, -1, 64)) return rc;
-    lo64 = 64;
-  }
-  // Round 6: the same split with the two launches BESIDE one another (an auxiliary stream, fork / join through events).  The kernel is bound by
-  // LDS per world (one-row instantiation 12.6 KB, two-row 23.7 KB: 8 against 6 worlds per CU on the G1), so the few-row worlds at their own
-  // size shorten the batch by a partial round -- as long as they do not wait for the many-row launch.  MJH_SOLVE64_SPLIT=0 / 1 (developer knob).
-  const int split_knob = KNOB_ONCE_INT("MJH_SOLVE64_SPLIT", MJH_SOLVE64_SPLIT_DEFAULT);
-  Aux* aux64 = (split_knob && !r1_64) ? aux_streams() : nullptr;
-  if (aux64) {
-    HIPCHK(hipEventRecord(aux64->fork, s));
-    HIPCHK(hipStreamWaitEvent(aux64->stream[0], aux64->fork, 0));
-    int rc = s64(m, d, 1, false, fe, aux64->stream[0], -1, 64);
-    if (!rc) {
-      if (d->njmax <= 128) rc = s64(m, d, 2, with_factor, fe, s, 64, all);
-      else {
-        rc = s64(m, d, 2, with_factor, fe, s, 64, 128);
-        if (!rc) rc = s64(m, d, 3, false, fe, s, 128, top);
-        if (!rc && d->njmax > 192) rc = launch_solve_big(m, d, s, 192);
-      }
-    }
-    HIPCHK(hipEventRecord(aux64->join[0], aux64->stream[0]));  // (every fork rejoins the caller's stream, also on the error path)
-    HIPCHK(hipStreamWaitEvent(s, aux64->join[0], 0));
-    return rc;
-  }
-  if (d->njmax <= 128) return s64(m, d, 2, with_factor, fe, s, lo64, all);
-  // Round 6: a launch's J tile is sized for the rows it can meet (solve_layout(min(njmax, hi))).  Lowering the two-row launch's bound to 112 rows
-  // fits one more G1 world per CU (19.3 instead of 21.7 KB: 8 instead of 7) -- measured, two interleaved rounds, bit-identical states: 9.54 M
-  // env-steps/s at 128, 9.47 at 112, 9.44 at 96: the launch is not bound by whole LDS rounds.  The bound stays 128; MJH_SOLVE64_HI2 (developer knob).
-  const int hi2_knob = KNOB_ONCE_INT("MJH_SOLVE64_HI2", 0);
-  const int hi2 = (hi2_knob >= 80 && hi2_knob <= 128) ? (hi2_knob & ~15) : 128;
-  if (int rc = s64(m, d, 2, with_factor, fe, s, lo64, hi2)) return rc;
-  if (int rc = s64(m, d, 3, false, fe, s, hi2, top)) return rc;
-  return d->njmax > 192 ? launch_solve_big(m, d, s, 192) : MJH_OK;
-}
 // the launches of the plan's solver family (fe: the solver's epilogue integrates; with_factor: the riders are its trailing workgroups)
 static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan& p, hipStream_t s) {
   const int fe = p.fuse_euler, all = 0x7fffffff;
@@ -656,25 +550,16 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan&
         if (cap >= 2 && cap <= MJH_NAUX) naux = cap;
       }
       // stream 0: islands of 8..16 dofs; 1: the generic solver (worlds with an island beyond 64 dofs); 2: 16..32 dofs; 3: many rows / 33..64 dofs.
-      // MJH_BIG_SHARES=1 (developer knob, A/B): the generic solver behind the 16..32-dof class on stream 2 -- four branches instead of five (the
-      // runtime has four hardware queues by default: R6.7).  Measured, two interleaved rounds: clutter_synth 1.55 / 1.54, three_humanoids
-      // 5.18 / 5.17 M env-steps/s -- nothing; off.
-      const bool big_shares = KNOB_ONCE_INT("MJH_BIG_SHARES", 0) != 0;
-      const bool share = big_shares && naux > 2;
-      bool used[MJH_NAUX] = {false, false, false, false};
-      for (int k = 0; k < naux; ++k) used[k] = !(share && k == 1);
-      hipStream_t s1 = aux ? aux->stream[0] : s, s3 = naux > 2 ? aux->stream[2] : s1, s4 = naux > 3 ? aux->stream[3] : s1;
-      hipStream_t s2 = !aux ? s : (share ? s3 : aux->stream[1]);
+      // (Retired experiment, LAB_NOTES.md R6.14: the generic solver behind the 16..32-dof class on stream 2, four branches instead of five -- nothing.)
+      hipStream_t s1 = aux ? aux->stream[0] : s, s2 = aux ? aux->stream[1] : s, s3 = naux > 2 ? aux->stream[2] : s1, s4 = naux > 3 ? aux->stream[3] : s1;
       if (aux) {
         HIPCHK(hipEventRecord(aux->fork, s));
-        for (int k = 0; k < naux; ++k)
-          if (used[k]) HIPCHK(hipStreamWaitEvent(aux->stream[k], aux->fork, 0));
+        for (int k = 0; k < naux; ++k) HIPCHK(hipStreamWaitEvent(aux->stream[k], aux->fork, 0));
       }
       int rc = (p.newton ? (p.ell ? launch_solve_tree_newton_ell : launch_solve_tree_newton) : (p.ell ? launch_solve_tree_cg_ell : launch_solve_tree_cg))(m, d, s, s1, s3, s4);
       if (!rc) rc = launch_solve_big(m, d, s2);
       if (aux) {  // (every fork rejoins the caller's stream, also on the error path: the streams may be under capture)
         for (int k = 0; k < naux; ++k) {
-          if (!used[k]) continue;
           HIPCHK(hipEventRecord(aux->join[k], aux->stream[k]));
           HIPCHK(hipStreamWaitEvent(s, aux->join[k], 0));
         }
@@ -712,7 +597,20 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan&
     case FAM_CG64:
     case FAM_CG64_ELL:
     case FAM_NEWTON64:
-    case FAM_NEWTON64_ELL: return launch_solve_rows_64(m, d, p, s);
+    case FAM_NEWTON64_ELL: {
+      // 64 lanes per world: 1 / 2 / 3 rows per lane cover 64 / 128 / 192 rows.  The second launch of a pair runs after the first on the same
+      // stream, so the split point is chosen to leave it (almost) empty: its real worlds would otherwise be a serial tail on an idle GPU (G1:
+      // 6 % of the worlds exceed 64 rows, practically none exceed 128).
+      // (Retired experiments, LAB_NOTES.md R6.5: the worlds of at most 64 rows in a one-row launch of their own, in front -- G1 7.84 vs 9.14 M
+      // env-steps/s -- or beside the others on an auxiliary stream -- 9.75 -> 9.64 M; the two-row launch bounded at 112 / 96 rows instead of 128 --
+      // 9.54 / 9.47 / 9.44 M.)
+      auto s64 = p.ell ? (p.newton ? launch_solve_64_newton_ell : launch_solve_64_cg_ell) : (p.newton ? launch_solve_64_newton : launch_solve_64_cg);
+      if (d->njmax <= 64) return s64(m, d, 1, with_factor, fe, s, -1, all);
+      if (d->njmax <= 128) return s64(m, d, 2, with_factor, fe, s, -1, all);
+      if (int rc = s64(m, d, 2, with_factor, fe, s, -1, 128)) return rc;
+      if (int rc = s64(m, d, 3, false, fe, s, 128, top)) return rc;
+      return d->njmax > 192 ? launch_solve_big(m, d, s, 192) : MJH_OK;
+    }
   }
   return fail(MJH_E_ARG, "launch_solve_any: unknown solver family");
 }
@@ -720,8 +618,8 @@ static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s) { re
 // name of the solver family of (m, d) in a fused step -- the plan, nothing launched
 static const char* solver_kernel_name(const MjhModel* m, const MjhData* d) { return kFamilyName[plan_step(m, d, MJH_STAGE_STEP, false).family]; }
 // integrator workgroups (integrate) and the riders -- contact publication, L'DL factor + qacc_smooth -- (with_factor)
-template <int G>
-static int launch_integrate_plus_g(const MjhModel* m, const MjhData* d, int mode, bool integrate, bool with_factor, hipStream_t s) {
+static int launch_integrate_plus(const MjhModel* m, const MjhData* d, int mode, bool integrate, bool with_factor, hipStream_t s) {
+  constexpr int G = 32;  // (see launch_factor_smooth)
   const IntLayout lay = int_layout(m->nv, m->nC);
   const FacLayout fl = fac_layout(m->nv, m->nC);
   const size_t ms_bytes = sizeof(int) * mstruct_ints(m->nv, m->nC);
@@ -737,7 +635,6 @@ static int launch_integrate_plus_g(const MjhModel* m, const MjhData* d, int mode
   hipLaunchKernelGGL(k_integrate_plus<G>, dim3(nint + npub + nfac), dim3(256), lds, s, *m, *d, mode, nint, npub);
   return MJH_OK;
 }
-static int launch_integrate_plus(const MjhModel* m, const MjhData* d, int mode, bool integrate, bool with_factor, hipStream_t s) { return launch_integrate_plus_g<32>(m, d, mode, integrate, with_factor, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 // *sched_done: whether the launch carried the schedule workgroup (it needs >= 128 threads to be quick; otherwise it
 // rides with k_mid, whose workgroups always have 256)
 // control noise queued by mjh_timed_steps for the next fused step: it rides with that step's first launch
@@ -752,10 +649,8 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
   if (!threads) return fail(MJH_E_UNSUPPORTED, "k_fwd_pos: model does not fit in LDS");
   // The schedule workgroup is this launch's first workgroup.  Round 5: its sort was a chain of 32 dependent memory round trips (13 us: the tail of
   // whichever launch carried it -- fused k_fwd_pos 48 us against 39 us without it); with its loads in one batch (integrate.hpp schedule_body) it
-  // costs this launch 2 us.  Same box, steady state / first steps, ms per step: here 0.2914 / 0.2698, as k_mid's last workgroup 0.2902 / 0.2745
-  // (MJH_SCHED_IN_MID=1, developer knob).
-  const bool sched_mid = KNOB_ONCE_FLAG("MJH_SCHED_IN_MID");
-  *sched_done = threads >= 128 && !sched_mid;
+  // costs this launch 2 us.  (Retired experiment, LAB_NOTES.md R5: always as k_mid's last workgroup -- 0.2902 / 0.2745 against 0.2914 / 0.2698 ms per step here.)
+  *sched_done = threads >= 128;
   if (threads < 128) {
     if (noise.n) hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
     return launch_pos(m, d, first, last, s);
@@ -768,7 +663,10 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
   hipLaunchKernelGGL(k_fwd_pos_plus<G>, dim3(npos + 1 + nnoise), dim3(threads), lds, s, *m, *d, first, last, npos, noise);
   return MJH_OK;
 }
-static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) { const bool pos16 = KNOB_ONCE_FLAG("MJH_LANES16_POS"); return lanes16(m) && pos16 ? launch_pos_plus_g<16>(m, d, first, last, sched_done, s) : lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, s) : launch_pos_plus_g<32>(m, d, first, last, sched_done, s); }
+// Never launched, kept instantiated: it shares the 16-lane helper functions with k_mid<16>, and without this second caller the compiler inlines and
+// allocates registers differently in k_mid<16> (24217 -> 24165 instructions).  It goes in a change that measures the Panda step (LAB_NOTES.md R6.14).
+template __global__ void k_fwd_pos_plus<16>(MjhModel, MjhData, int, int, int, NoiseArgs);
+static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) { return lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, s) : launch_pos_plus_g<32>(m, d, first, last, sched_done, s); }  // (never 16 lanes: see lanes16)
 
 
 static int check(const MjhModel* m, const MjhData* d) {
@@ -839,20 +737,16 @@ static Side* side_stream() {
     Side* sd = new Side();
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
-    // developer knob (A/B): "high" / "normal"; default: the lowest priority.  Measured (round 3, two interleaved triples on one box): no
-    // difference (0.2810 / 0.2803 / 0.2805 ms per Newton step) -- queue priority does not arbitrate CU slots.  The riders still end ~20 us
-    // after the solver (rocprofv3 timeline, profiles/round3_newton_summary.json): their workgroups only get slots as the solver's retire
-    const char* pe = knob_str("MJH_SIDE_PRIO");
-    const int prio = pe && pe[0] == 'h' ? greatest : (pe && pe[0] == 'n' ? 0 : least);
     // Round 6: the side stream IS the first auxiliary stream of the per-island solver (aux_streams; the two are never used by the same step).
     // A stream of its own cost every later model of the process its solver concurrency: once it existed -- any Newton model of at most 32
     // dofs stepped earlier -- the four class launches of clutter_synth ran 25 % slower (1.43 -> 1.07 M env-steps/s, tools/interference_probe.py:
-    // the runtime multiplexes user streams onto a few hardware queues, and streams that share one run in order).  MJH_SIDE_PRIO (a priority of
-    // its own) therefore implies a stream of its own.
-    Aux* shared = pe ? nullptr : aux_streams();
+    // the runtime multiplexes user streams onto a few hardware queues, and streams that share one run in order).  Without auxiliary streams
+    // (MJH_NO_AUX, instrumentation): a stream of its own at the lowest priority.  (Retired experiment, LAB_NOTES.md R3: high / normal priority
+    // -- no difference, queue priority does not arbitrate CU slots; the riders' workgroups only get slots as the solver's retire.)
+    Aux* shared = aux_streams();
     sd->owns_stream = shared == nullptr;
     if (shared) sd->stream = shared->stream[0];
-    if ((sd->owns_stream && hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, prio) != hipSuccess) ||
+    if ((sd->owns_stream && hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, least) != hipSuccess) ||
         hipEventCreateWithFlags(&sd->fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&sd->join, hipEventDisableTiming) != hipSuccess) {
       delete sd;
@@ -1037,14 +931,9 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         HIPCHK(hipEventRecord(side->fork, s));
         HIPCHK(hipStreamWaitEvent(side->stream, side->fork, 0));
         // both riders as roles of ONE launch (k_integrate_plus without integrator workgroups): their two chains overlap and one launch gap
-        // goes (round 3, same-box A/B in two interleaved pairs: humanoid Newton 0.2842 -> 0.2829 / 0.2835 -> 0.2822 ms, Panda 142.9 -> 142.0 us)
-        const bool side_two = KNOB_ONCE_FLAG("MJH_SIDE_TWO");  // developer knob (A/B): the two plain kernels of round 2
-        if (!side_two) {
-          TRY(launch_integrate_plus(m, d, p.mode, false, true, side->stream));
-        } else {
-          TRY(launch_publish(m, d, side->stream));
-          TRY(launch_factor_smooth(m, d, 1, side->stream));
-        }
+        // goes (round 3, same-box A/B in two interleaved pairs against the two plain kernels of round 2: humanoid Newton 0.2842 -> 0.2829 /
+        // 0.2835 -> 0.2822 ms, Panda 142.9 -> 142.0 us; the two-kernel form is retired)
+        TRY(launch_integrate_plus(m, d, p.mode, false, true, side->stream));
         HIPCHK(hipEventRecord(side->join, side->stream));
       }
       { Scope sc(K_SOLVE); TRY(launch_solve_any(m, d, p, s)); }
@@ -1058,19 +947,12 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
   }
 }
 
-template <int G>
-static int launch_solve_m_g(const MjhModel* m, const MjhData* d, float* x, const float* y, int mul, hipStream_t s) {
+static int launch_solve_m(const MjhModel* m, const MjhData* d, float* x, const float* y, int mul, hipStream_t s) {
   const IntLayout lay = int_layout(m->nv, m->nC);
-  size_t lds;
-  const int threads = pick_block(sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, G, &lds);
-  if (!threads) return fail(MJH_E_UNSUPPORTED, "k_solve_m: does not fit in LDS");
-  HIPCHK(set_lds(k_solve_m<G>, lds));
-  const int wpb = threads / G;
-  hipLaunchKernelGGL(k_solve_m<G>, dim3((d->nworld + wpb - 1) / wpb), dim3(threads), lds, s, *m, *d, x, y, mul);
+  TRY(launch_per_world(k_solve_m<32>, "k_solve_m: does not fit in LDS", 32, sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, d->nworld, s, *m, *d, x, y, mul));  // (see launch_factor_smooth)
   HIPCHK(hipGetLastError());
   return MJH_OK;
 }
-static int launch_solve_m(const MjhModel* m, const MjhData* d, float* x, const float* y, int mul, hipStream_t s) { return launch_solve_m_g<32>(m, d, x, y, mul, s); }  // (chains over the sparse factor: more lanes per world only halve the worlds per wavefront)
 
 // the C ABI is the only exported surface (the library is built with -fvisibility=hidden)
 #pragma GCC visibility push(default)

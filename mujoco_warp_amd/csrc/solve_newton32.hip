@@ -42,11 +42,9 @@ static int launch_newton_t(const MjhModel* m, const MjhData* d, int fuse_euler, 
   return MJH_OK;
 }
 int launch_solve_newton_mfma(const MjhModel* m, const MjhData* d, bool with_factor, int fuse_euler, hipStream_t s) {
-  // two wavefronts per SIMD is the measured optimum: at three (168 VGPRs) the register allocator still spills in the Cholesky
-  const bool w2 = KNOB_ONCE_INT("MJH_NEWTON_WAVES", 2) == 2;  // developer knob
-  return dispatch_nv4_32((m->nv + 3) / 4, [&](auto NV4) {
-    return w2 ? launch_newton_t<NV4(), 2>(m, d, fuse_euler, with_factor, s) : launch_newton_t<NV4(), 3>(m, d, fuse_euler, with_factor, s);
-  });
+  // two wavefronts per SIMD (WV, part of the kernels' symbols) is the measured optimum: at three (168 VGPRs) the register allocator still
+  // spills in the Cholesky -- that second set of instantiations is retired
+  return dispatch_nv4_32((m->nv + 3) / 4, [&](auto NV4) { return launch_newton_t<NV4(), 2>(m, d, fuse_euler, with_factor, s); });
 }
 
 int launch_solve_32_newton(const MjhModel* m, const MjhData* d, int nr, bool with_factor, int fuse_euler, hipStream_t s, int lo, int hi) {

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Did a change move device code?  Compares the gfx950 code objects of two builds unit by unit, kernel by kernel.
 
-    python tools/compare_device_code.py <objdir-A> <objdir-B>
+    python tools/compare_device_code.py [--removed <regex>]... <objdir-A> <objdir-B>
 
 <objdir>: a directory holding the builder's objects, `<unit>.o` or the object cache's `<unit>.<key>.o` (build/objcache of a checkout;
 build the two commits in separate checkouts so that each has its own).  For every unit of _abi.UNITS: the set of kernel symbols, each
 kernel's metadata (the amdhsa.kernels note: VGPR / SGPR / AGPR counts, LDS, scratch, kernarg size, arguments) and its disassembled
-instruction stream with addresses stripped.  Exit status 0 when everything is identical -- the bar for a host-only change.
+instruction stream with addresses stripped (branch targets are relative; the pc-relative offset of another symbol -- the literal of the
+s_add_u32 behind an s_getpc_b64 -- moves whenever a unit gains or loses code and is masked).  Exit status 0 when everything is identical -- the bar for a host-only change.
+--removed <regex> (repeatable) names kernels that B is meant to have dropped: a symbol of A alone that matches one in full is listed, not counted.
+Everything else still fails: a kernel only in B, an unnamed kernel only in A, any metadata or code difference, and a regex that matched nothing.
 """
 
 import glob
@@ -55,7 +58,11 @@ def kernels_of(path):
     for blk in re.split(r"\n(?=[0-9a-f]+ <[^>]+>:)", dis):
       mm = re.match(r"[0-9a-f]+ <([^>]+)>:\n", blk)
       if mm:
-        code[mm.group(1)] = "\n".join(re.sub(r"\s*//.*$", "", ln).rstrip() for ln in blk[mm.end():].splitlines())
+        lines = [re.sub(r"\s*//.*$", "", ln).rstrip() for ln in blk[mm.end():].splitlines()]
+        for i in range(1, len(lines)):  # the pc-relative offset of another symbol (s_getpc_b64 + s_add_u32 <literal>) is an address: it moves with the unit's layout
+          if lines[i - 1].lstrip().startswith("s_getpc_b64"):
+            lines[i] = re.sub(r"^(\s*s_add_u32 (s\d+), \2, )\S+$", r"\1<pcrel>", lines[i])
+        code[mm.group(1)] = "\n".join(lines)
     meta = {}
     kern = notes[notes.index("amdhsa.kernels:"):] if "amdhsa.kernels:" in notes else ""
     kern = re.split(r"\n(?=amdhsa\.\w+:)", kern)[0]
@@ -75,12 +82,21 @@ def find(objdir, unit):
   return hits[0]
 
 
-def main(a, b):
+def main(a, b, removed=()):
   bad = 0
   total = 0
+  hits = {r: 0 for r in removed}
   for unit in UNITS:
     ka, kb = kernels_of(find(a, unit)), kernels_of(find(b, unit))
-    only = sorted(set(ka) ^ set(kb))
+    only = []
+    for k in sorted(set(ka) ^ set(kb)):
+      named = [r for r in removed if k in ka and re.fullmatch(r, k)]
+      for r in named:
+        hits[r] += 1
+      if named:
+        print(f"     removed as named: {k}")
+      else:
+        only.append(k)
     diff_meta = [k for k in sorted(set(ka) & set(kb)) if ka[k][0] != kb[k][0]]
     diff_code = [k for k in sorted(set(ka) & set(kb)) if ka[k][1] != kb[k][1]]
     ninstr = sum(len(v[1].splitlines()) for v in ka.values())
@@ -89,11 +105,19 @@ def main(a, b):
     for k in only + diff_meta + diff_code:
       print("    ", k)
     bad += len(only) + len(diff_meta) + len(diff_code)
-  print(f"{total} kernels compared: " + ("device code IDENTICAL" if not bad else f"{bad} DIFFERENCES"))
+  for r, n in hits.items():
+    print(f"--removed {r}: {n} kernels")
+    bad += n == 0
+  gone = sum(hits.values())
+  print(f"{total} kernels compared: " + ((f"{gone} removed as named, the other " if gone else "") + "device code IDENTICAL" if not bad else f"{bad} DIFFERENCES"))
   return 1 if bad else 0
 
 
 if __name__ == "__main__":
-  if len(sys.argv) != 3:
+  args, removed = sys.argv[1:], []
+  while len(args) >= 2 and args[0] == "--removed":
+    removed.append(args[1])
+    args = args[2:]
+  if len(args) != 2:
     raise SystemExit(__doc__)
-  sys.exit(main(sys.argv[1], sys.argv[2]))
+  sys.exit(main(args[0], args[1], removed))
