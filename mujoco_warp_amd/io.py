@@ -1,10 +1,16 @@
 """Host <-> device IO: the drop-in boundary of the engine.
 
-Mirrors /root/reference/mujoco_warp/_src/io.py: put_model 259 (validation 284-360, derived tables 495-652),
+Mirrors the reference's mujoco_warp/_src/io.py: put_model 259 (validation 284-360, derived tables 495-652),
 make_data 1680, put_data 1890, get_data_into 2184, reset_data 2435, reset_data_keyframe 2797,
 override_model 2933; default sizing _default_nconmax 1284 / _default_njmax 1299 / _get_padded_sizes 1268.
 Same signatures, shapes, dtypes and error behaviour (ValueError / NotImplementedError at put/make time;
 capacity problems at run time are bits in `d.overflow`).
+
+Shapes and dtypes are stated once, in types.py (types.array_fields); the header says which of the arrays the library reads.  put_model
+runs named phases (_check_supported, _tree_tables, _collision_facts, _actuator_facts, _options), each returning the sizes and host arrays
+it derives; every other MjhModel array is the host model's attribute of that name, cast and reshaped to its declaration (_host_array,
+_OPTIONAL_FIELDS for what a host model may lack).  make_data / put_data allocate every MjhData array from its declaration in the sizes of
+_data_sizes.
 """
 
 import ctypes
@@ -19,8 +25,17 @@ from .device import DeviceArray
 from .mjcf import SENS as mjcf_SENS  # mjtSensor values of the supported sensors
 
 _BATCHED_MODEL_FIELDS = [n[:-3] for n, k, p in _abi.MODEL_FIELDS if n.endswith("_nb")]
-_MODEL_PTR_FIELDS = [(n, k) for n, k, p in _abi.MODEL_FIELDS if p]
-_DATA_PTR_FIELDS = [(n, k) for n, k, p in _abi.DATA_FIELDS if p]
+_MODEL_PTR_FIELDS = [n for n, k, p in _abi.MODEL_FIELDS if p]
+_DATA_PTR_FIELDS = [n for n, k, p in _abi.DATA_FIELDS if p]
+
+
+def _declared(*prefixed):
+  """{ABI name: (shape, dtype, host)} of the arrays the given (prefix, class) pairs declare."""
+  return {prefix + name: decl for prefix, cls in prefixed for name, decl in types.array_fields(cls).items()}
+
+
+_MODEL_ARRAYS = _declared(("opt_", types.Option), ("stat_", types.Statistic), ("", types.Model))
+_DATA_ARRAYS = _declared(("contact_", types.Contact), ("efc_", types.Constraint), ("", types.Data))
 
 
 def _valid_sizes():
@@ -168,15 +183,23 @@ def cull_tables(geom_bodyid, pairs, pairid, geom_pos=None, geom_rbound=None):
   return cgeom.astype(i32), np.stack([centre, count], axis=1).astype(i32), cp.astype(i32), cl.astype(i32)
 
 
-def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
-  """Creates a model on device (reference io.py:259).
+def _condims(mjm, pairs):
+  """condim values of the colliding geoms and of the explicit pairs."""
+  condims = set(int(c) for c in np.unique(np.asarray(mjm.geom_condim)[np.unique(pairs)])) if len(pairs) else set()
+  if int(getattr(mjm, "npair", 0)):
+    condims |= set(int(c) for c in np.asarray(mjm.pair_dim))
+  return condims
 
-  Args:
-    mjm: compiled model (mujoco.MjModel, or the numpy stand-in built by mujoco_warp_amd.mjcf).
-    batch_sizes: optional {field name: nworld} making "*" fields per-world (domain randomisation).
-  """
+
+def _pair_types(mjm, pairs):
+  """(smaller, larger) geom type of every pair."""
+  gt = np.asarray(mjm.geom_type)
+  return [(int(min(gt[a], gt[b])), int(max(gt[a], gt[b]))) for a, b in pairs]
+
+
+def _check_supported(mjm, pairs):
+  """Refuses what this engine does not compute (reference io.py:284-360): physics must not be dropped silently."""
   opt = mjm.opt
-  # ---- validation (io.py:284-360) ----
   if int(getattr(mjm, "neq", 0)) > 0 and (np.asarray(mjm.eq_type) != types.EqType.JOINT).any():
     raise NotImplementedError("only joint equality constraints are implemented")
   for name in ("ntendon", "nflex", "nplugin"):
@@ -213,7 +236,6 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   for name in ("jnt_stiffnesspoly", "dof_dampingpoly"):
     if np.asarray(getattr(mjm, name, [0.0])).any():
       raise NotImplementedError(f"{name} (polynomial stiffness / damping) is not implemented.")
-  # physics this engine does not compute must not be dropped silently
   if float(getattr(opt, "density", 0.0)) != 0.0 or float(getattr(opt, "viscosity", 0.0)) != 0.0:
     raise NotImplementedError("fluid forces (option density / viscosity, passive.py _fluid_force) are not implemented.")
   unsupported_enable = int(opt.enableflags) & int(types.EnableBit.OVERRIDE | types.EnableBit.FWDINV | types.EnableBit.INVDISCRETE)
@@ -224,11 +246,8 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     raise ValueError(f"sleeping requires the Newton solver (got solver={types.SolverType(int(opt.solver)).name})")
   if (int(opt.enableflags) & int(types.EnableBit.SLEEP)) and int(opt.integrator) == int(types.IntegratorType.RK4):
     raise NotImplementedError("sleeping with the RK4 integrator is not implemented.")
-  pairs, pairid = geom_pairs_with_ids(mjm)
-  cull = cull_tables(mjm.geom_bodyid, pairs, pairid, mjm.geom_pos, mjm.geom_rbound)
   gt = np.asarray(mjm.geom_type)
-  for a, b in pairs:
-    t = (int(min(gt[a], gt[b])), int(max(gt[a], gt[b])))
+  for (a, b), t in zip(pairs, _pair_types(mjm, pairs)):
     if t in ((0, 1), (1, 1)):
       continue  # (plane / height-field against a height field: no collider in the reference either, collision_driver.py:47-59)
     if t not in _SUPPORTED_PAIRS and t not in _CONVEX_PAIRS and t != _PLANE_MESH and t not in _HFIELD_PAIRS:
@@ -240,75 +259,83 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
         mid = int(np.asarray(getattr(mjm, "geom_dataid", np.full(len(gt), -1)))[g])
         if mid < 0 or not hasattr(mjm, "mesh_vert"):
           raise NotImplementedError("colliding mesh geom without mesh vertices (Model.mesh_vert / geom_dataid)")
-  condims = set(int(c) for c in np.unique(np.asarray(mjm.geom_condim)[np.unique(pairs)])) if len(pairs) else set()
-  nexplicit = int(getattr(mjm, "npair", 0))
-  if nexplicit:
-    condims |= set(int(c) for c in np.asarray(mjm.pair_dim))
+  condims = _condims(mjm, pairs)
   if not condims <= {1, 3, 4, 6}:
     raise NotImplementedError(f"unsupported condim values {condims}")
 
-  ngeom_ = int(mjm.ngeom)
-  m = types.Model()
-  nv, nbody, njnt, ngeom, nu = int(mjm.nv), int(mjm.nbody), int(mjm.njnt), int(mjm.ngeom), int(mjm.nu)
-  for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nkey", "nmocap"):
-    setattr(m, name, int(getattr(mjm, name, 0)))
-  for name in ("neq", "ntendon", "nsensor", "nmesh", "nflex", "nhfield", "ncam", "nlight"):
-    setattr(m, name, int(getattr(mjm, name, 0)))
-  m.nC = int(np.sum(mjm.M_rownnz)) if nv else 0
-  m.nM = m.nC
-  # capsule-box / box-box pairs and explicit contact pairs select the kernel instantiation that carries them (include/mjhip.h)
-  ptypes = [(int(min(gt[a], gt[b])), int(max(gt[a], gt[b]))) for a, b in pairs]
+
+def _collision_facts(mjm, pairs, pairid):
+  """(sizes and flags, host arrays) of the collision pipeline: which kernel instantiation the model's pairs need, the buffers of the convex
+  narrowphase, the pair tables."""
+  opt, ngeom, nexplicit = mjm.opt, int(mjm.ngeom), int(getattr(mjm, "npair", 0))
+  ptypes = _pair_types(mjm, pairs)
   # box-box is a CONVEX pair (GJK / EPA + multi-contact) unless DisableBit.NATIVECCD selects the primitive collider
   # (reference collision_driver.py:78, 867-870)
   box_ccd = not (int(opt.disableflags) & int(types.DisableBit.NATIVECCD))
   nboxbox = sum(t == (6, 6) for t in ptypes) if box_ccd else 0
   nconvex = sum(t in _CONVEX_PAIRS or t in _HFIELD_PAIRS for t in ptypes)
-  m._convex_pairs = int(nconvex + nboxbox > 0)
+  convex_pairs = int(nconvex + nboxbox > 0)
+  # capsule-box / box-box pairs and explicit contact pairs select the kernel instantiation that carries them (include/mjhip.h)
+  heavy = int(any(t in ((3, 6), (6, 6), (0, 7)) for t in ptypes) or nexplicit > 0 or convex_pairs)
   # EPA iteration cap (reference collision_convex.py:1223): 16 when every convex pair of the model is box-box
-  m._epa_iterations = 16 if (nboxbox > 0 and nconvex == 0) else int(getattr(opt, "ccd_iterations", 35))
-  m._heavy_pairs = int(any((int(min(gt[a], gt[b])), int(max(gt[a], gt[b]))) in ((3, 6), (6, 6), (0, 7)) for a, b in pairs) or int(getattr(mjm, "npair", 0)) > 0
-                       or m._convex_pairs)
-  m.heavy_colliders = m._heavy_pairs  # c_model() adds the broadphase options (they may be changed after put_model)
-  # mesh geoms a ray could hit (visible colour: the reference's _ray_eliminate keeps them, ray.py:52) whose mesh carries no triangles
-  # (Model.mesh_face; a visual mesh whose asset was never loaded has none): rays() and the rangefinder sensor refuse such a model instead
-  # of silently reporting "no hit".  Meshes with triangles and height fields are intersected (csrc/ray.hpp)
-  g_rgba = np.asarray(getattr(mjm, "geom_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (ngeom, 1))), dtype=np.float64).reshape(-1, 4)
-  g_mat = np.asarray(getattr(mjm, "geom_matid", np.full(ngeom, -1))).reshape(-1)
-  m_rgba = np.asarray(getattr(mjm, "mat_rgba", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4)
-  g_data = np.asarray(getattr(mjm, "geom_dataid", np.full(ngeom, -1))).reshape(-1)
-  mesh_nface = _mesh_face_counts(mjm)
-  no_tri = [g for g in range(ngeom) if int(gt[g]) == int(types.GeomType.MESH) and (m_rgba[g_mat[g], 3] if g_mat[g] >= 0 else g_rgba[g, 3]) != 0.0
+  epa_iterations = 16 if (nboxbox > 0 and nconvex == 0) else int(getattr(opt, "ccd_iterations", 35))
+  # clip buffers of the multi-contact recovery: 2 * npolygonmax points (reference collision_convex.py:1226-1234)
+  nboxmesh, nmeshmesh = sum(t == (6, 7) for t in ptypes), sum(t == (7, 7) for t in ptypes)
+  npolygonmax, nmeshdegmax = 4 if nboxbox > 0 else 0, 0
+  if not (int(opt.disableflags) & int(types.DisableBit.MULTICCD)) and nboxmesh + nmeshmesh > 0:
+    polyvertnum, polymapnum = np.asarray(getattr(mjm, "mesh_polyvertnum", ())), np.asarray(getattr(mjm, "mesh_polymapnum", ()))
+    npolygonmax = max(int(polyvertnum.max()) if polyvertnum.size else 0, 4 if nboxmesh else npolygonmax)
+    # polygons around one vertex (collision_convex.py:1233 nmeshdegmax): sizes the normal / index buffers of the multi-contact recovery
+    nmeshdegmax = max(int(polymapnum.max()) if polymapnum.size else 0, 3)
+  condims = _condims(mjm, pairs)
+  nmaxcondim = int(max(condims)) if condims else 1
+  # condim of every contact the model can make (collision_core.py contact_params: the geom of higher priority decides, the larger condim
+  # at equal priority; explicit pairs carry their own): only 1 and 3 -> CG may run the contact-basis kernel (csrc/solver_cgp.hpp)
+  gc_, gp_ = np.asarray(mjm.geom_condim).astype(int), np.asarray(mjm.geom_priority).astype(int)
+  pair_condims = set(int(gc_[a] if gp_[a] > gp_[b] else gc_[b] if gp_[b] > gp_[a] else max(gc_[a], gc_[b])) for a, b in pairs)
+  if nexplicit:
+    pair_condims |= set(int(c) for c in np.asarray(mjm.pair_dim))
+  # ... and no friction-loss rows (their three-zone cost is outside that kernel: it would hand EVERY world to its fallback launch, which
+  # solves flagged worlds one after the other -- ADVICE round 5); the kernel still defers a world that shows up with nf > 0 (a model whose
+  # frictionloss was edited after put_model), so this flag is about speed, not correctness
+  has_floss = bool(np.any(np.asarray(getattr(mjm, "dof_frictionloss", 0.0)) > 0)) or bool(np.any(np.asarray(getattr(mjm, "tendon_frictionloss", 0.0)) > 0))
+  cull = cull_tables(mjm.geom_bodyid, pairs, pairid, mjm.geom_pos, mjm.geom_rbound)
+  facts = dict(
+    _convex_pairs=convex_pairs, _epa_iterations=epa_iterations, epa_iterations=epa_iterations, _heavy_pairs=heavy,
+    heavy_colliders=heavy,  # c_model() adds the broadphase options (they may be changed after put_model)
+    npolygonmax=npolygonmax, nmeshdegmax=nmeshdegmax, nmaxcondim=nmaxcondim, nmaxpyramid=max(1, 2 * (nmaxcondim - 1)),
+    cg_basis=int(pair_condims <= {1, 3} and not has_floss), npair=int(len(pairs)), nexplicit=nexplicit,
+    ncullgeom=int(len(cull[0])), ncullgroup=int(len(cull[1])), ncullpair=int(len(cull[2])))
+  return facts, dict(nxn_geom_pair=pairs, nxn_pairid=pairid, nxn_pairindex=_pair_index(ngeom, pairs),
+                     cull_geom=cull[0], cull_group=cull[1], cull_pair=cull[2], cull_list=cull[3])
+
+
+def _ray_facts(host):
+  """Mesh geoms a ray could hit (visible colour: the reference's _ray_eliminate keeps them, ray.py:52) whose mesh carries no triangles
+  (Model.mesh_face; a visual mesh whose asset was never loaded has none): rays() and the rangefinder sensor refuse such a model instead
+  of silently reporting "no hit".  Meshes with triangles and height fields are intersected (csrc/ray.hpp)."""
+  gt, g_rgba, g_mat, g_data, m_rgba = host["geom_type"], host["geom_rgba"], host["geom_matid"], host["geom_dataid"], host["mat_rgba"]
+  mesh_nface = _mesh_face_counts(host)
+  no_tri = [g for g in range(len(gt)) if int(gt[g]) == int(types.GeomType.MESH) and (m_rgba[g_mat[g], 3] if g_mat[g] >= 0 else g_rgba[g, 3]) != 0.0
             and (g_data[g] < 0 or g_data[g] >= len(mesh_nface) or mesh_nface[g_data[g]] == 0)]
-  m._ray_unsupported_geoms = len(no_tri)
-  # their geom groups (clamped to 0..5 as the ray elimination does): a rays() call whose geomgroup hides all of them is served
-  g_group = np.asarray(getattr(mjm, "geom_group", np.zeros(ngeom))).reshape(-1)
-  m._ray_unsupported_groups = sorted(set(min(5, max(0, int(g_group[g]))) for g in no_tri))
-  if m._ray_unsupported_geoms and any(int(t) == 7 for t in np.asarray(getattr(mjm, "sensor_type", np.zeros(0))).reshape(-1)):
+  if no_tri and (host["sensor_type"] == 7).any():
     raise NotImplementedError("rangefinder sensor in a model with visible mesh geoms that have no triangles (Model.mesh_face): rays against those geoms "
                               "would be reported as no hit; make them invisible to rays (rgba alpha 0), load their mesh or drop the sensor")
-  m.is_sparse = False
+  # their geom groups (clamped to 0..5 as the ray elimination does): a rays() call whose geomgroup hides all of them is served
+  return dict(_ray_unsupported_geoms=len(no_tri), _ray_unsupported_groups=sorted(set(min(5, max(0, int(host["geom_group"][g]))) for g in no_tri)))
 
-  m.nv_pad = _get_padded_sizes(nv, 1)[1]
 
-  # ---- options (io.py:392-470) ----
-  o = types.Option()
-  o._root = m
-  f32 = np.float32
-  o.timestep = np.array([opt.timestep], dtype=f32)
-  # float32 device arithmetic cannot resolve MuJoCo's default 1e-8 (io.py:398-401)
-  o.tolerance = np.array([max(float(opt.tolerance), 1e-6)], dtype=f32)
-  o.ls_tolerance = np.array([opt.ls_tolerance], dtype=f32)
-  o.gravity = _arr(opt.gravity, f32).reshape(1, 3)
-  o.impratio_invsqrt = np.array([1.0 / np.sqrt(max(float(opt.impratio), types.MJ_MINVAL))], dtype=f32)
-  o.ccd_tolerance = np.array([float(getattr(opt, "ccd_tolerance", 1e-6))], dtype=f32)
-  o.magnetic = _arr(getattr(opt, "magnetic", [0.0, -0.5, 0.0]), f32).reshape(1, 3)
+def _options(mjm, m):
+  """(Option with its integers, Statistic, their host arrays under the ABI names opt_* / stat_*) (reference io.py:392-470)."""
+  opt, f32 = mjm.opt, np.float32
+  o, s = types.Option(), types.Statistic()
+  o._root = s._root = m
   for name in ("integrator", "cone", "solver", "iterations", "ls_iterations", "disableflags", "enableflags"):
     setattr(o, name, int(getattr(opt, name)))
   o.ccd_iterations = int(getattr(opt, "ccd_iterations", 35))
-  m.epa_iterations = m._epa_iterations
   # reference io.py:631-636: NXN below 250k filtered pairs, SAP above (tile sort below 1000 geoms)
-  o.broadphase = (types.BroadphaseType.NXN if len(pairs) < 250_000 else
-                  types.BroadphaseType.SAP_TILE if ngeom_ < 1000 else types.BroadphaseType.SAP_SEGMENTED)
+  o.broadphase = (types.BroadphaseType.NXN if m.npair < 250_000 else
+                  types.BroadphaseType.SAP_TILE if m.ngeom < 1000 else types.BroadphaseType.SAP_SEGMENTED)
   # the reference's default adds the OBB filter (io.py:405); contacts do not depend on the filter set (every filter is
   # conservative), only Data.ncollision does, and plane + sphere keeps the light collision kernel (DESIGN.md)
   o.broadphase_filter = types.BroadphaseFilter.PLANE | types.BroadphaseFilter.SPHERE
@@ -319,20 +346,31 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   o.graph_conditional = False
   o.run_collision_detection = True
   o.warn_overflow = False
-  s = types.Statistic()
-  s._root = m
-  s.meaninertia = np.array([mjm.stat.meaninertia], dtype=f32)
+  return o, s, dict(
+    opt_timestep=np.array([opt.timestep], dtype=f32),
+    # float32 device arithmetic cannot resolve MuJoCo's default 1e-8 (io.py:398-401)
+    opt_tolerance=np.array([max(float(opt.tolerance), 1e-6)], dtype=f32),
+    opt_ls_tolerance=np.array([opt.ls_tolerance], dtype=f32), opt_gravity=_arr(opt.gravity, f32).reshape(1, 3),
+    opt_impratio_invsqrt=np.array([1.0 / np.sqrt(max(float(opt.impratio), types.MJ_MINVAL))], dtype=f32),
+    opt_ccd_tolerance=np.array([float(getattr(opt, "ccd_tolerance", 1e-6))], dtype=f32),
+    opt_magnetic=_arr(getattr(opt, "magnetic", [0.0, -0.5, 0.0]), f32).reshape(1, 3),
+    stat_meaninertia=np.array([mjm.stat.meaninertia], dtype=f32))
 
-  # ---- derived tables ----
+
+def _level_order(parent):
+  """(ids in order of depth, stable; where every depth level starts in that order) of a forest given by parent ids: a root's is negative or its own."""
+  depth = np.zeros(len(parent), dtype=np.int32)
+  for i, p in enumerate(parent):
+    depth[i] = 0 if p < 0 or p == i else depth[p] + 1
+  return np.argsort(depth, kind="stable").astype(np.int32), np.concatenate([[0], np.cumsum(np.bincount(depth))]).astype(np.int32)
+
+
+def _tree_tables(mjm):
+  """(sizes and flags, host arrays) derived from the kinematic tree: body / dof level orders, subtree counts, last dofs, the kinematic trees and
+  the size classes of the per-tree and island solver kernels."""
+  nv, nbody = int(mjm.nv), int(mjm.nbody)
   parent = _arr(mjm.body_parentid, np.int32)
-  depth = np.zeros(nbody, dtype=np.int32)
-  for b in range(1, nbody):
-    depth[b] = depth[parent[b]] + 1
-  order = np.argsort(depth, kind="stable").astype(np.int32)
-  nlevel = int(depth.max()) + 1 if nbody else 0
-  leveladr = np.zeros(nlevel + 1, dtype=np.int32)
-  for l in range(nlevel):
-    leveladr[l + 1] = leveladr[l] + int(np.sum(depth == l))
+  order, leveladr = _level_order(parent)
   subtreenum = np.ones(nbody, dtype=np.int32)
   for b in range(nbody - 1, 0, -1):
     subtreenum[parent[b]] += subtreenum[b]
@@ -356,29 +394,13 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     if not (dof_treeid[r : r + tree_dofnum[t]] == t).all():
       raise ValueError("dofs of a kinematic tree must be contiguous (MuJoCo order)")
   body_treeid = np.array([dof_treeid[lastdof[b]] if lastdof[b] >= 0 else -1 for b in range(nbody)], dtype=np.int32)
-  m.ntree = len(roots)
-  if mjm.nu:
-    adof = np.asarray(mjm.jnt_dofadr)[np.asarray(mjm.actuator_trnid).reshape(-1, 2)[:, 0]]
-    m.act_dof_max = int(np.bincount(adof, minlength=max(nv, 1)).max())
-    # d(force)/d(velocity) of an actuator = gainprm[2] * ctrl (affine gain) + biasprm[2] (affine bias): non-positive for every ctrl only
-    # without a gain term and with biasprm[2] <= 0 (a position servo's -kv); otherwise the implicitfast matrix can lose definiteness
-    gp, bp = np.asarray(mjm.actuator_gainprm, dtype=np.float64).reshape(nu, -1), np.asarray(mjm.actuator_biasprm, dtype=np.float64).reshape(nu, -1)
-    gt_, bt_ = np.asarray(mjm.actuator_gaintype).reshape(-1), np.asarray(mjm.actuator_biastype).reshape(-1)
-    m.act_velfeedback = int(bool(((gt_ == 1) & (gp[:, 2] != 0.0)).any() or ((bt_ == 1) & (bp[:, 2] > 0.0)).any()))
-  else:
-    m.act_dof_max = 0
-    m.act_velfeedback = 0
-  m.tree_nvmax = int(tree_dofnum.max()) if len(roots) else 0
-  # nv > 64: worlds whose rows each touch one kinematic tree are solved per (world, tree) by the register-resident kernels
-  m.tree_solve = int(nv > 64 and m.ntree > 1 and m.tree_nvmax <= 64 and int(opt.solver) != types.SolverType.PGS)
+  ntree, tree_nvmax = len(roots), int(tree_dofnum.max()) if len(roots) else 0
   # size classes of the island kernels: islands of <= 32 dofs run with 32 lanes and ceil(dofs / 4) quarter-rows -- the widest one is a
   # single tree unless two trees together fit --, islands of 33..64 dofs with 64 lanes
   small = sorted(int(n) for n in tree_dofnum if n <= 32)
   widest = max(small) if small else 0
   if len(small) >= 2 and small[0] + small[1] <= 32:
     widest = 32
-  m.isl_nv4 = (widest + 3) // 4
-  m.isl_wide = int(nv > 32)
   nw = max((nv + 31) // 32, 1)
   dofmask = np.zeros((nbody, nw), dtype=np.uint32)
   for b in range(nbody):  # io.py:536-549 body_isdofancestor as bit masks
@@ -386,16 +408,8 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     while dsel >= 0:
       dofmask[b, dsel >> 5] |= np.uint32(1 << (dsel & 31))
       dsel = dof_parent[dsel]
-  ddepth = np.zeros(nv, dtype=np.int32)
-  for i in range(nv):
-    ddepth[i] = 0 if dof_parent[i] < 0 else ddepth[dof_parent[i]] + 1
-  dorder = np.argsort(ddepth, kind="stable").astype(np.int32)
-  ndlevel = int(ddepth.max()) + 1 if nv else 0
-  dleveladr = np.zeros(ndlevel + 1, dtype=np.int32)
-  for l in range(ndlevel):
-    dleveladr[l + 1] = dleveladr[l] + int(np.sum(ddepth == l))
-  jnt_type, jnt_dofadr = _arr(mjm.jnt_type, np.int32), _arr(mjm.jnt_dofadr, np.int32)
-  dof_jnt = _arr(mjm.dof_jntid, np.int32)
+  dorder, dleveladr = _level_order(dof_parent)
+  jnt_type, jnt_dofadr, dof_jnt = np.asarray(mjm.jnt_type), np.asarray(mjm.jnt_dofadr), np.asarray(mjm.dof_jntid)
   grpadr = np.arange(nv, dtype=np.int32)
   for i in range(nv):
     j = dof_jnt[i]
@@ -403,113 +417,113 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
       grpadr[i] = jnt_dofadr[j]
     elif jnt_type[j] == types.JointType.FREE and i - jnt_dofadr[j] >= 3:
       grpadr[i] = jnt_dofadr[j] + 3
+  facts = dict(
+    ntree=ntree, tree_nvmax=tree_nvmax, nbodylevel=len(leveladr) - 1, ndoflevel=len(dleveladr) - 1, isl_nv4=(widest + 3) // 4, isl_wide=int(nv > 32),
+    # nv > 64: worlds whose rows each touch one kinematic tree are solved per (world, tree) by the register-resident kernels
+    tree_solve=int(nv > 64 and ntree > 1 and tree_nvmax <= 64 and int(mjm.opt.solver) != types.SolverType.PGS))
+  return facts, dict(body_lastdof=lastdof, body_subtreenum=subtreenum, body_tree=order, body_leveladr=leveladr, body_dofmask=dofmask,
+                     dof_grpadr=grpadr, dof_tree=dorder, dof_leveladr=dleveladr, tree_dofadr=tree_dofadr, tree_dofnum=tree_dofnum,
+                     dof_treeid=dof_treeid, body_treeid=body_treeid)
 
-  host = {}  # name -> numpy array in ABI dtype
-  i32 = np.int32
-  host.update(
-    opt_timestep=o.timestep, opt_tolerance=o.tolerance, opt_ls_tolerance=o.ls_tolerance, opt_gravity=o.gravity,
-    opt_impratio_invsqrt=o.impratio_invsqrt, opt_ccd_tolerance=o.ccd_tolerance, opt_magnetic=o.magnetic, stat_meaninertia=s.meaninertia,
-    qpos0=_arr(mjm.qpos0, f32).reshape(1, -1), qpos_spring=_arr(mjm.qpos_spring, f32).reshape(1, -1),
-    body_parentid=parent, body_rootid=_arr(mjm.body_rootid, i32), body_weldid=_arr(mjm.body_weldid, i32),
-    body_jntnum=_arr(mjm.body_jntnum, i32), body_jntadr=_arr(mjm.body_jntadr, i32), body_dofnum=dofnum, body_dofadr=dofadr,
-    body_lastdof=lastdof, body_mocapid=_arr(getattr(mjm, "body_mocapid", np.full(nbody, -1)), i32), body_subtreenum=subtreenum, body_tree=order, body_leveladr=leveladr, body_dofmask=dofmask,
-    jnt_type=jnt_type, jnt_qposadr=_arr(mjm.jnt_qposadr, i32), jnt_dofadr=jnt_dofadr, jnt_bodyid=_arr(mjm.jnt_bodyid, i32),
-    jnt_limited=_arr(mjm.jnt_limited, i32),
-    jnt_actfrclimited=_arr(getattr(mjm, "jnt_actfrclimited", np.zeros(njnt)), i32), jnt_actgravcomp=_arr(getattr(mjm, "jnt_actgravcomp", np.zeros(njnt)), i32),
-    jnt_actfrcrange=_arr(getattr(mjm, "jnt_actfrcrange", np.zeros((njnt, 2))), f32).reshape(1, njnt, 2),
-    dof_bodyid=_arr(mjm.dof_bodyid, i32), dof_jntid=dof_jnt, dof_parentid=dof_parent, dof_grpadr=grpadr, dof_tree=dorder,
-    dof_leveladr=dleveladr, tree_dofadr=tree_dofadr, tree_dofnum=tree_dofnum, dof_treeid=dof_treeid, body_treeid=body_treeid,
-    M_rownnz=_arr(mjm.M_rownnz, i32), M_rowadr=_arr(mjm.M_rowadr, i32), M_colind=_arr(mjm.M_colind, i32), M_dense=_m_dense(mjm, nv),
-    geom_type=_arr(mjm.geom_type, i32), geom_condim=_arr(mjm.geom_condim, i32), geom_bodyid=_arr(mjm.geom_bodyid, i32),
-    geom_priority=_arr(mjm.geom_priority, i32), geom_group=_arr(getattr(mjm, "geom_group", np.zeros(ngeom)), i32),
-    geom_matid=_arr(getattr(mjm, "geom_matid", np.full(ngeom, -1)), i32), geom_rgba=_arr(getattr(mjm, "geom_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (ngeom, 1))), f32).reshape(-1, 4),
-    mat_rgba=_arr(getattr(mjm, "mat_rgba", np.zeros((0, 4))), f32).reshape(-1, 4), geom_dataid=_arr(getattr(mjm, "geom_dataid", np.full(ngeom, -1)), i32),
-    mesh_vertadr=_arr(getattr(mjm, "mesh_vertadr", np.zeros(0)), i32), mesh_vertnum=_arr(getattr(mjm, "mesh_vertnum", np.zeros(0)), i32),
-    mesh_vert=_arr(getattr(mjm, "mesh_vert", np.zeros((0, 3))), f32).reshape(-1, 3),
-    mesh_face=_arr(getattr(mjm, "mesh_face", np.zeros((0, 3))), i32).reshape(-1, 3), mesh_faceadr=_arr(getattr(mjm, "mesh_faceadr", np.zeros(0)), i32),
-    sensor_type=_arr(getattr(mjm, "sensor_type", np.zeros(0)), i32), sensor_datatype=_arr(getattr(mjm, "sensor_datatype", np.zeros(0)), i32),
-    sensor_objtype=_arr(getattr(mjm, "sensor_objtype", np.zeros(0)), i32), sensor_objid=_arr(getattr(mjm, "sensor_objid", np.zeros(0)), i32),
-    sensor_reftype=_arr(getattr(mjm, "sensor_reftype", np.zeros(0)), i32), sensor_refid=_arr(getattr(mjm, "sensor_refid", np.zeros(0)), i32),
-    sensor_dim=_arr(getattr(mjm, "sensor_dim", np.zeros(0)), i32), sensor_adr=_arr(getattr(mjm, "sensor_adr", np.zeros(0)), i32),
-    sensor_cutoff=_arr(getattr(mjm, "sensor_cutoff", np.zeros(0)), f32),
-    hfield_size=_arr(getattr(mjm, "hfield_size", np.zeros((0, 4))), f32).reshape(-1, 4), hfield_nrow=_arr(getattr(mjm, "hfield_nrow", np.zeros(0)), i32),
-    hfield_ncol=_arr(getattr(mjm, "hfield_ncol", np.zeros(0)), i32), hfield_adr=_arr(getattr(mjm, "hfield_adr", np.zeros(0)), i32),
-    hfield_data=_arr(getattr(mjm, "hfield_data", np.zeros(0)), f32),
-    mesh_graphadr=_arr(getattr(mjm, "mesh_graphadr", np.full(int(getattr(mjm, "nmesh", 0)), -1)), i32), mesh_graph=_arr(getattr(mjm, "mesh_graph", np.zeros(0)), i32),
-    mesh_polyadr=_arr(getattr(mjm, "mesh_polyadr", np.zeros(0)), i32), mesh_polynormal=_arr(getattr(mjm, "mesh_polynormal", np.zeros((0, 3))), f32).reshape(-1, 3),
-    mesh_polyvertadr=_arr(getattr(mjm, "mesh_polyvertadr", np.zeros(0)), i32), mesh_polyvertnum=_arr(getattr(mjm, "mesh_polyvertnum", np.zeros(0)), i32),
-    mesh_polyvert=_arr(getattr(mjm, "mesh_polyvert", np.zeros(0)), i32), mesh_polymapadr=_arr(getattr(mjm, "mesh_polymapadr", np.zeros(0)), i32),
-    mesh_polymapnum=_arr(getattr(mjm, "mesh_polymapnum", np.zeros(0)), i32), mesh_polymap=_arr(getattr(mjm, "mesh_polymap", np.zeros(0)), i32), nxn_geom_pair=pairs, nxn_pairid=pairid, nxn_pairindex=_pair_index(ngeom, pairs),
-    cull_geom=cull[0], cull_group=cull[1], cull_pair=cull[2], cull_list=cull[3],
-    pair_dim=_arr(getattr(mjm, "pair_dim", np.zeros(0)), i32), pair_friction=_arr(getattr(mjm, "pair_friction", np.zeros((0, 5))), f32).reshape(-1, 5),
-    pair_solref=_arr(getattr(mjm, "pair_solref", np.zeros((0, 2))), f32).reshape(-1, 2),
-    pair_solreffriction=_arr(getattr(mjm, "pair_solreffriction", np.zeros((0, 2))), f32).reshape(-1, 2),
-    pair_solimp=_arr(getattr(mjm, "pair_solimp", np.zeros((0, 5))), f32).reshape(-1, 5),
-    pair_margin=_arr(getattr(mjm, "pair_margin", np.zeros(0)), f32), pair_gap=_arr(getattr(mjm, "pair_gap", np.zeros(0)), f32),
-    site_bodyid=_arr(getattr(mjm, "site_bodyid", np.zeros(0)), i32),
-    site_type=_arr(getattr(mjm, "site_type", np.full(int(getattr(mjm, "nsite", 0)), 2)), i32), site_size=_arr(getattr(mjm, "site_size", np.full((int(getattr(mjm, "nsite", 0)), 3), 0.005)), f32).reshape(-1, 3),
-    actuator_dyntype=_arr(mjm.actuator_dyntype, i32), actuator_gaintype=_arr(mjm.actuator_gaintype, i32),
-    actuator_biastype=_arr(mjm.actuator_biastype, i32), actuator_trnid=_arr(mjm.actuator_trnid, i32).reshape(-1, 2),
-    actuator_actadr=_arr(mjm.actuator_actadr, i32), actuator_ctrllimited=_arr(mjm.actuator_ctrllimited, i32),
-    actuator_forcelimited=_arr(mjm.actuator_forcelimited, i32), actuator_actlimited=_arr(mjm.actuator_actlimited, i32),
-    eq_obj1id=_arr(getattr(mjm, "eq_obj1id", np.zeros(0)), i32), eq_obj2id=_arr(getattr(mjm, "eq_obj2id", np.zeros(0)), i32),
-  )
-  m.nsensor, m.nsensordata = int(host["sensor_type"].shape[0]), int(getattr(mjm, "nsensordata", 0))
-  supported_sensors = set(mjcf_SENS.values())
-  m.nsensor_acc = int(sum(int(t) in (0, 1, 4, 5, 22, 33, 34) for t in host["sensor_type"]))
-  m.nsensor_energy = int(sum(int(t) in (43, 44) for t in host["sensor_type"]))
-  m.nsensor_frc = int(sum(int(t) in (4, 5) for t in host["sensor_type"]))
-  m.nsensor_subtree = int(sum(int(t) in (36, 37) for t in host["sensor_type"]))
-  bad = [int(t) for t in host["sensor_type"] if int(t) not in supported_sensors]
+
+def _actuator_facts(mjm):
+  """act_dof_max and act_velfeedback."""
+  nv, nu = int(mjm.nv), int(mjm.nu)
+  if not nu:
+    return dict(act_dof_max=0, act_velfeedback=0)
+  adof = np.asarray(mjm.jnt_dofadr)[np.asarray(mjm.actuator_trnid).reshape(-1, 2)[:, 0]]
+  # d(force)/d(velocity) of an actuator = gainprm[2] * ctrl (affine gain) + biasprm[2] (affine bias): non-positive for every ctrl only
+  # without a gain term and with biasprm[2] <= 0 (a position servo's -kv); otherwise the implicitfast matrix can lose definiteness
+  gp, bp = np.asarray(mjm.actuator_gainprm, dtype=np.float64).reshape(nu, -1), np.asarray(mjm.actuator_biasprm, dtype=np.float64).reshape(nu, -1)
+  gt, bt = np.asarray(mjm.actuator_gaintype).reshape(-1), np.asarray(mjm.actuator_biastype).reshape(-1)
+  return dict(act_dof_max=int(np.bincount(adof, minlength=max(nv, 1)).max()),
+              act_velfeedback=int(bool(((gt == 1) & (gp[:, 2] != 0.0)).any() or ((bt == 1) & (bp[:, 2] > 0.0)).any())))
+
+
+# Model arrays a host model may lack, and what stands in for them: a value fills the declared shape (a property the model's objects have by
+# default); None is an empty table (the model has no such objects).
+_OPTIONAL_FIELDS = {
+  "geom_matid": -1, "geom_dataid": -1, "body_mocapid": -1, "mesh_graphadr": -1, "site_type": 2, "site_size": 0.005,
+  "geom_rgba": [0.5, 0.5, 0.5, 1.0], "tree_sleep_policy": int(types.SleepPolicy.AUTO_ALLOWED), "dof_length": 1,
+  "jnt_actfrclimited": 0, "jnt_actgravcomp": 0, "jnt_actfrcrange": 0, "geom_group": 0,
+  **dict.fromkeys(
+    """mat_rgba mesh_vertadr mesh_vertnum mesh_vert mesh_face mesh_faceadr mesh_graph mesh_polyadr mesh_polynormal mesh_polyvertadr
+    mesh_polyvertnum mesh_polyvert mesh_polymapadr mesh_polymapnum mesh_polymap hfield_size hfield_nrow hfield_ncol hfield_adr hfield_data
+    sensor_type sensor_datatype sensor_objtype sensor_objid sensor_reftype sensor_refid sensor_dim sensor_adr sensor_cutoff
+    pair_dim pair_friction pair_solref pair_solreffriction pair_solimp pair_margin pair_gap site_bodyid site_pos site_quat
+    eq_obj1id eq_obj2id eq_solref eq_solimp eq_data""".split()),
+}
+# sizes the Model takes from the length of one of its arrays (the host model's own counters are not consulted)
+_SIZE_FROM_ARRAY = {"nsensor": "sensor_type", "nmesh": "mesh_vertadr", "nmeshvert": "mesh_vert", "nmeshface": "mesh_face", "nmeshpoly": "mesh_polyvertnum",
+                    "nmeshgraph": "mesh_graph", "nmeshpolyvert": "mesh_polyvert", "nmeshpolymap": "mesh_polymap", "nhfield": "hfield_nrow",
+                    "nhfielddata": "hfield_data", "nmat": "mat_rgba"}
+# ... and -1 in a reshape; so are the site and explicit-pair counts: their optional tables are empty when absent, whatever the counters say
+_FREE_SIZES = dict.fromkeys([*_SIZE_FROM_ARRAY, "nsite", "nexplicit"], -1)
+
+
+def _host_array(mjm, name, sizes):
+  """The host model's array `name` in the dtype and shape types.Model declares ('*' = 1), or its _OPTIONAL_FIELDS stand-in."""
+  shape, dtype, _ = _MODEL_ARRAYS[name]
+  dims = lambda env: [1 if n == "*" else n for n in types.eval_shape(shape, env)]
+  src = getattr(mjm, name, None)
+  if src is None:
+    if name not in _OPTIONAL_FIELDS:
+      raise AttributeError(f"model is missing field {name}")
+    fill = _OPTIONAL_FIELDS[name]
+    src = np.zeros(0) if fill is None else np.broadcast_to(fill, dims(sizes))
+  return _arr(src, dtype).reshape(dims({**sizes, **_FREE_SIZES}))
+
+
+def _sensor_facts(sensor_type):
+  """Counts of the sensor classes the stages of csrc/sensor.hpp are launched for."""
+  supported = set(mjcf_SENS.values())
+  bad = [int(t) for t in sensor_type if int(t) not in supported]
   if bad:  # (sensors do not enter the dynamics: the model still loads, their sensordata slots stay zero)
     import warnings
 
-    warnings.warn(f"sensor types {sorted(set(bad))} are not computed by this engine (csrc/sensor.hpp computes {sorted(supported_sensors)}): their sensordata entries are 0")
-  m.nmeshvert = int(host["mesh_vert"].shape[0])
-  m.nmeshface = int(host["mesh_face"].shape[0])
-  m.nmeshpoly = int(host["mesh_polyvertnum"].shape[0])
-  m.nmeshgraph = int(host["mesh_graph"].shape[0])
-  m.nhfield, m.nhfielddata = int(host["hfield_nrow"].shape[0]), int(host["hfield_data"].shape[0])
-  m.nmeshpolyvert, m.nmeshpolymap = int(host["mesh_polyvert"].shape[0]), int(host["mesh_polymap"].shape[0])
-  # clip buffers of the multi-contact recovery: 2 * npolygonmax points (reference collision_convex.py:1226-1234)
-  nboxmesh, nmeshmesh = sum(t == (6, 7) for t in ptypes), sum(t == (7, 7) for t in ptypes)
-  m.npolygonmax = 4 if nboxbox > 0 else 0
-  if not (int(opt.disableflags) & int(types.DisableBit.MULTICCD)) and nboxmesh + nmeshmesh > 0:
-    m.npolygonmax = max(int(host["mesh_polyvertnum"].max()) if m.nmeshpoly else 0, 4 if nboxmesh else m.npolygonmax)
-    # polygons around one vertex (collision_convex.py:1233 nmeshdegmax): sizes the normal / index buffers of the multi-contact recovery
-    m.nmeshdegmax = max(int(host["mesh_polymapnum"].max()) if len(host["mesh_polymapnum"]) else 0, 3)
-  m.nmesh = int(host["mesh_vertadr"].shape[0])
-  m.nmat = int(host["mat_rgba"].shape[0])
+    warnings.warn(f"sensor types {sorted(set(bad))} are not computed by this engine (csrc/sensor.hpp computes {sorted(supported)}): their sensordata entries are 0")
+  count = lambda kinds: int(sum(int(t) in kinds for t in sensor_type))
+  return dict(nsensor_acc=count((0, 1, 4, 5, 22, 33, 34)), nsensor_energy=count((43, 44)), nsensor_frc=count((4, 5)), nsensor_subtree=count((36, 37)))
+
+
+def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
+  """Creates a model on device (reference io.py:259).
+
+  Args:
+    mjm: compiled model (mujoco.MjModel, or the numpy stand-in built by mujoco_warp_amd.mjcf).
+    batch_sizes: optional {field name: nworld} making "*" fields per-world (domain randomisation).
+  """
+  opt, nv = mjm.opt, int(mjm.nv)
+  pairs, pairid = geom_pairs_with_ids(mjm)
+  _check_supported(mjm, pairs)
+  m = types.Model()
+  for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nkey", "nmocap", "neq", "ntendon", "nsensor", "nmesh", "nflex", "nhfield",
+               "ncam", "nlight", "nsensordata"):
+    setattr(m, name, int(getattr(mjm, name, 0)))
+  m.nC = m.nM = int(np.sum(mjm.M_rownnz)) if nv else 0
+  m.is_sparse = False
+  m.nv_pad = _get_padded_sizes(nv, 1)[1]
+  host = {"M_dense": _m_dense(mjm, nv)}  # ABI name -> numpy array in the declared dtype
+  for facts, arrays in (_tree_tables(mjm), _collision_facts(mjm, pairs, pairid), (_actuator_facts(mjm), {})):
+    for name, value in facts.items():
+      setattr(m, name, value)
+    host.update(arrays)
+  o, s, arrays = _options(mjm, m)
+  host.update(arrays)
+  sizes = {k: v for k, v in vars(m).items() if isinstance(v, int) and not k.startswith("_")}
+  for name in _MODEL_PTR_FIELDS:
+    if name not in host:
+      host[name] = _host_array(mjm, name, sizes)
+  for size, name in _SIZE_FROM_ARRAY.items():
+    setattr(m, size, int(host[name].shape[0]))
+  for name, value in {**_sensor_facts(host["sensor_type"]), **_ray_facts(host)}.items():
+    setattr(m, name, value)
   m.sleep_enabled = int(bool(int(opt.enableflags) & int(types.EnableBit.SLEEP)) and not (int(opt.disableflags) & int(types.DisableBit.ISLAND)))
   m.opt_sleep_tolerance = float(getattr(opt, "sleep_tolerance", 1e-4))
-  host["tree_sleep_policy"] = _arr(getattr(mjm, "tree_sleep_policy", np.full(m.ntree, int(types.SleepPolicy.AUTO_ALLOWED))), i32)
-  host["dof_length"] = _arr(getattr(mjm, "dof_length", np.ones(nv)), f32)
   if m.sleep_enabled and (host["tree_sleep_policy"] > int(types.SleepPolicy.AUTO_ALLOWED)).any():
     raise NotImplementedError("sleep policies NEVER / ALLOWED / INIT are not implemented (reference types.py:308).")
-  neq = int(getattr(mjm, "neq", 0))
-  host["eq_solref"] = _arr(getattr(mjm, "eq_solref", np.zeros((0, 2))), f32).reshape(1, neq, 2)
-  host["eq_solimp"] = _arr(getattr(mjm, "eq_solimp", np.zeros((0, 5))), f32).reshape(1, neq, 5)
-  host["eq_data"] = _arr(getattr(mjm, "eq_data", np.zeros((0, 11))), f32).reshape(1, neq, 11)
-  m.eq_active0 = _arr(getattr(mjm, "eq_active0", np.zeros(0)), i32)
-  vec = {"geom_aabb": 6, "body_pos": 3, "body_quat": 4, "body_ipos": 3, "body_iquat": 4, "body_inertia": 3, "body_invweight0": 2,
-         "jnt_solref": 2, "jnt_solimp": 5, "jnt_pos": 3, "jnt_axis": 3, "jnt_range": 2, "jnt_actfrcrange": 2, "dof_solref": 2, "dof_solimp": 5,
-         "geom_solref": 2, "geom_solimp": 5, "geom_size": 3, "geom_pos": 3, "geom_quat": 4, "geom_friction": 3,
-         "site_pos": 3, "site_quat": 4, "actuator_dynprm": 10, "actuator_gainprm": 10, "actuator_biasprm": 10,
-         "actuator_ctrlrange": 2, "actuator_forcerange": 2, "actuator_actrange": 2, "actuator_gear": 6}
-  for name in _BATCHED_MODEL_FIELDS:
-    if name in host:
-      continue
-    src = getattr(mjm, name, None)
-    if src is None:
-      if name in ("site_pos", "site_quat"):
-        src = np.zeros((0, vec[name]))
-      else:
-        raise AttributeError(f"model is missing field {name}")
-    a = _arr(src, f32)
-    host[name] = a.reshape(1, -1, vec[name]) if name in vec else a.reshape(1, -1)
 
-  batch_sizes = batch_sizes or {}
-  for name, n in batch_sizes.items():
+  for name, n in (batch_sizes or {}).items():
     key = {"timestep": "opt_timestep", "tolerance": "opt_tolerance", "gravity": "opt_gravity",
            "meaninertia": "stat_meaninertia"}.get(name, name)
     if key not in _BATCHED_MODEL_FIELDS:
@@ -517,7 +531,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     host[key] = np.repeat(host[key][:1], int(n), axis=0)
 
   # ---- upload; public attribute names follow the reference Model ----
-  for name, kind in _MODEL_PTR_FIELDS:
+  for name in _MODEL_PTR_FIELDS:
     da = DeviceArray.from_numpy(host[name])
     if name.startswith("opt_"):
       setattr(o, name[4:], da)
@@ -526,32 +540,12 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     else:
       setattr(m, name, da)
   m.opt, m.stat = o, s
-  m.npair = int(len(pairs))
-  m.ncullgeom, m.ncullgroup, m.ncullpair = int(len(cull[0])), int(len(cull[1])), int(len(cull[2]))
-  m.nexplicit = nexplicit
   m.nxn_geom_pair_filtered = m.nxn_geom_pair
-  m.nbodylevel, m.ndoflevel = nlevel, ndlevel
-  m.nmaxcondim = int(max(condims)) if condims else 1
-  m.nmaxpyramid = max(1, 2 * (m.nmaxcondim - 1))
-  # condim of every contact the model can make (collision_core.py contact_params: the geom of higher priority decides, the larger condim
-  # at equal priority; explicit pairs carry their own): only 1 and 3 -> CG may run the contact-basis kernel (csrc/solver_cgp.hpp)
-  gc_, gp_ = np.asarray(mjm.geom_condim).astype(int), np.asarray(mjm.geom_priority).astype(int)
-  pair_condims = set(int(gc_[a] if gp_[a] > gp_[b] else gc_[b] if gp_[b] > gp_[a] else max(gc_[a], gc_[b])) for a, b in pairs)
-  if nexplicit:
-    pair_condims |= set(int(c) for c in np.asarray(mjm.pair_dim))
-  # ... and no friction-loss rows (their three-zone cost is outside that kernel: it would hand EVERY world to its fallback launch, which
-  # solves flagged worlds one after the other -- ADVICE round 5); the kernel still defers a world that shows up with nf > 0 (a model whose
-  # frictionloss was edited after put_model), so this flag is about speed, not correctness
-  has_floss = bool(np.any(np.asarray(getattr(mjm, "dof_frictionloss", 0.0)) > 0)) or bool(np.any(np.asarray(getattr(mjm, "tendon_frictionloss", 0.0)) > 0))
-  m.cg_basis = int(pair_condims <= {1, 3} and not has_floss)
   m._ccd_flags_at_put = int(opt.disableflags)
-  m.key_qpos = _arr(getattr(mjm, "key_qpos", np.zeros((0, m.nq))), f32)
-  m.key_qvel = _arr(getattr(mjm, "key_qvel", np.zeros((0, nv))), f32)
-  m.key_ctrl = _arr(getattr(mjm, "key_ctrl", np.zeros((0, nu))), f32)
-  m.key_mpos = _arr(getattr(mjm, "key_mpos", np.zeros((0, 3 * m.nmocap))), f32)
-  m.key_mquat = _arr(getattr(mjm, "key_mquat", np.zeros((0, 4 * m.nmocap))), f32)
-  m.key_act = _arr(getattr(mjm, "key_act", np.zeros((0, m.na))), f32)
-  m.key_time = _arr(getattr(mjm, "key_time", np.zeros(0)), f32)
+  m.eq_active0 = _arr(getattr(mjm, "eq_active0", np.zeros(0)), np.int32)
+  for name, width in (("key_qpos", m.nq), ("key_qvel", nv), ("key_ctrl", m.nu), ("key_mpos", 3 * m.nmocap), ("key_mquat", 4 * m.nmocap), ("key_act", m.na)):
+    setattr(m, name, _arr(getattr(mjm, name, np.zeros((0, width))), np.float32))
+  m.key_time = _arr(getattr(mjm, "key_time", np.zeros(0)), np.float32)
   m._dirty = True
   m._c = None
   return m
@@ -569,23 +563,54 @@ def _m_dense(mjm, nv):
   return t[:nv] if nv else t[:0]
 
 
-def _mesh_face_counts(mjm):
-  """Triangles per mesh of `mjm` (Model.mesh_face / mesh_faceadr; empty when the model has none), after checking that every index stays
+def _mesh_face_counts(host):
+  """Triangles per mesh (host arrays mesh_face / mesh_faceadr; empty when the model has none), after checking that every index stays
   inside its mesh's vertex block: the ray kernels read the vertices through them."""
-  adr = np.asarray(getattr(mjm, "mesh_faceadr", np.zeros(0)), dtype=np.int64).reshape(-1)
-  face = np.asarray(getattr(mjm, "mesh_face", np.zeros((0, 3))), dtype=np.int64).reshape(-1, 3)
-  nmesh = len(np.asarray(getattr(mjm, "mesh_vertadr", np.zeros(0))).reshape(-1))
+  adr, face, nmesh = host["mesh_faceadr"].astype(np.int64), host["mesh_face"].astype(np.int64), len(host["mesh_vertadr"])
   if len(adr) == 0 and len(face) == 0:
     return np.zeros(nmesh, dtype=np.int64)
   if len(adr) != nmesh or (np.diff(np.concatenate([[0], adr, [len(face)]])) < 0).any():
     raise ValueError("mesh_faceadr must have one non-decreasing entry per mesh, within mesh_face")
   num = np.diff(np.concatenate([adr, [len(face)]]))
-  vnum = np.asarray(mjm.mesh_vertnum, dtype=np.int64).reshape(-1)
+  vnum = host["mesh_vertnum"]
   for i in range(nmesh):
     f = face[adr[i] : adr[i] + num[i]]
     if len(f) and (f.min() < 0 or f.max() >= vnum[i]):
       raise ValueError(f"mesh {i}: face index outside its {vnum[i]} vertices")
   return num
+
+
+def _c_disableflags(m):
+  # the convex narrowphase's buffers (Model.nmeshdegmax / npolygonmax, Data.ws_ccd) were sized from these two bits at put_model /
+  # make_data; the reference re-derives them at every call (collision_convex.py:1226, 1346-1366), this engine cannot: a change needs a new
+  # put_model (kernels that branch on the live flags would run past buffers sized for the old ones)
+  ccd_bits = int(types.DisableBit.NATIVECCD) | int(types.DisableBit.MULTICCD)
+  if (int(m.opt.disableflags) ^ int(m._ccd_flags_at_put)) & ccd_bits:
+    raise ValueError("opt.disableflags: NATIVECCD / MULTICCD changed after put_model -- the convex narrowphase's buffers were sized from them; call put_model again")
+  return int(m.opt.disableflags)
+
+
+def _c_heavy_colliders(m):
+  bf_ = int(m.opt.broadphase_filter)
+  if bf_ & ~0xF:
+    raise ValueError(f"unknown broadphase filter bits {bf_:#x}")
+  if int(m.opt.broadphase) not in (0, 1, 2):
+    raise ValueError(f"unknown broadphase {int(m.opt.broadphase)}")
+  if int(m.opt.broadphase) == 0 and m._convex_pairs and int(m.npair) > 0 and int(m.ncullpair) == 0:
+    # (ADVICE round 5: io.cull_tables declines models beyond its 16-bit geom / 24-bit pair packing -- put_model picks SAP for those; NXN
+    # forced on one would fail every step with MJH_E_ARG in launch_ccd_pre: say so here)
+    raise NotImplementedError(f"opt.broadphase = NXN with convex pairs needs the pair-group tables, which hold at most 65535 geoms and 2^24 pairs "
+                              f"(this model: {int(m.ngeom)} geoms, {int(m.npair)} pairs): use SAP")
+  # (the light instantiation hard-wires plane + sphere and NXN and has no sleep filter)
+  return int(bool(m._heavy_pairs or bf_ != 3 or int(m.opt.broadphase) != 0 or m.sleep_enabled))
+
+
+# scalars of MjhModel that are not plain Model attributes of the same name
+_C_MODEL_SCALARS = {
+  **{name: (lambda m, name=name: int(getattr(m.opt, name)))
+     for name in ("integrator", "cone", "solver", "iterations", "ls_iterations", "enableflags", "broadphase", "broadphase_filter", "ccd_iterations")},
+  "disableflags": _c_disableflags, "opt_sleep_tolerance": lambda m: float(m.opt_sleep_tolerance), "heavy_colliders": _c_heavy_colliders,
+}
 
 
 def c_model(m: types.Model):
@@ -599,33 +624,8 @@ def c_model(m: types.Model):
       setattr(c, name, src.ptr)
       if name in _BATCHED_MODEL_FIELDS:
         setattr(c, name + "_nb", src.shape[0])
-    elif name.endswith("_nb"):
-      continue
-    elif name in ("integrator", "cone", "solver", "iterations", "ls_iterations", "disableflags", "enableflags", "broadphase", "broadphase_filter", "ccd_iterations"):
-      if name == "disableflags":
-        # the convex narrowphase's buffers (Model.nmeshdegmax / npolygonmax, Data.ws_ccd) were sized from these two bits at put_model /
-        # make_data; the reference re-derives them at every call (collision_convex.py:1226, 1346-1366), this engine cannot: a change needs a new
-        # put_model (kernels that branch on the live flags would run past buffers sized for the old ones)
-        ccd_bits = int(types.DisableBit.NATIVECCD) | int(types.DisableBit.MULTICCD)
-        if (int(m.opt.disableflags) ^ int(m._ccd_flags_at_put)) & ccd_bits:
-          raise ValueError("opt.disableflags: NATIVECCD / MULTICCD changed after put_model -- the convex narrowphase's buffers were sized from them; call put_model again")
-      setattr(c, name, int(getattr(m.opt, name)))
-    elif name == "opt_sleep_tolerance":
-      setattr(c, name, float(m.opt_sleep_tolerance))
-    elif name == "heavy_colliders":
-      bf_ = int(m.opt.broadphase_filter)
-      if bf_ & ~0xF:
-        raise ValueError(f"unknown broadphase filter bits {bf_:#x}")
-      if int(m.opt.broadphase) not in (0, 1, 2):
-        raise ValueError(f"unknown broadphase {int(m.opt.broadphase)}")
-      if int(m.opt.broadphase) == 0 and m._convex_pairs and int(m.npair) > 0 and int(m.ncullpair) == 0:
-        # (io.cull_tables declines models beyond its 16-bit geom / 24-bit pair packing -- put_model picks SAP for those; NXN
-        # forced on one would fail every step with MJH_E_ARG in launch_ccd_pre: say so here)
-        raise NotImplementedError(f"opt.broadphase = NXN with convex pairs needs the pair-group tables, which hold at most 65535 geoms and 2^24 pairs "
-                                  f"(this model: {int(m.ngeom)} geoms, {int(m.npair)} pairs): use SAP")
-      setattr(c, name, int(bool(m._heavy_pairs or bf_ != 3 or int(m.opt.broadphase) != 0 or m.sleep_enabled)))  # (sleep filter: heavy instantiation only)  # (the light instantiation hard-wires plane + sphere)
-    else:
-      setattr(c, name, int(getattr(m, name)))
+    elif not name.endswith("_nb"):
+      setattr(c, name, _C_MODEL_SCALARS[name](m) if name in _C_MODEL_SCALARS else int(getattr(m, name)))
   object.__setattr__(m, "_c", c)
   object.__setattr__(m, "_dirty", False)
   return c
@@ -665,42 +665,25 @@ def contact_cap(nconmax: int) -> int:
   return int(min(max(2 * nconmax, 16), 256))
 
 
-def _data_shapes(m, nworld, nconmax, njmax, naconmax, handcap=None):
-  njmax_pad, nv_pad = _get_padded_sizes(m.nv, njmax)
-  nb, nv, nq, nu, na, ng, nj, ns, nC = m.nbody, m.nv, m.nq, m.nu, m.na, m.ngeom, m.njnt, m.nsite, m.nC
-  W = nworld
-  sh = dict(
-    time=(W,), qpos=(W, nq), qvel=(W, nv), act=(W, na), ctrl=(W, nu), qacc_warmstart=(W, nv), qfrc_applied=(W, nv),
-    xfrc_applied=(W, nb, 6), mocap_pos=(W, m.nmocap, 3), mocap_quat=(W, m.nmocap, 4), xpos=(W, nb, 3), xquat=(W, nb, 4), xmat=(W, nb, 3, 3), xipos=(W, nb, 3), ximat=(W, nb, 3, 3),
-    xanchor=(W, nj, 3), xaxis=(W, nj, 3), geom_xpos=(W, ng, 3), geom_xmat=(W, ng, 3, 3), site_xpos=(W, ns, 3),
-    site_xmat=(W, ns, 3, 3), subtree_com=(W, nb, 3), cinert=(W, nb, 10), cdof=(W, nv, 6), crb=(W, nb, 10), M=(W, nC),
-    qLD=(W, nC), qLDiagInv=(W, nv), actuator_length=(W, nu), actuator_moment=(W, nu), actuator_velocity=(W, nu),
-    cvel=(W, nb, 6), cdof_dot=(W, nv, 6), qfrc_spring=(W, nv), qfrc_damper=(W, nv), qfrc_gravcomp=(W, nv),
-    qfrc_passive=(W, nv), qfrc_bias=(W, nv), cacc=(W, nb, 6), cfrc_int=(W, nb, 6), act_dot=(W, na),
-    actuator_force=(W, nu), qfrc_actuator=(W, nv), qfrc_smooth=(W, nv), qacc_smooth=(W, nv), qacc=(W, nv),
-    qfrc_constraint=(W, nv), efc_Ma=(W, nv), solver_niter=(W,), ne=(W,), nf=(W,), nl=(W,), nefc=(W,), overflow=(W,),
-    nacon=(1,), ncollision=(1,),
-    contact_dist=(naconmax,), contact_pos=(naconmax, 3), contact_frame=(naconmax, 3, 3), contact_includemargin=(naconmax,),
-    contact_friction=(naconmax, 5), contact_solref=(naconmax, 2), contact_solreffriction=(naconmax, 2),
-    contact_solimp=(naconmax, 5), contact_dim=(naconmax,), contact_geom=(naconmax, 2),
-    contact_efc_address=(naconmax, m.nmaxpyramid), contact_worldid=(naconmax,), contact_type=(naconmax,),
-    contact_geomcollisionid=(naconmax,),
-    efc_type=(W, njmax), efc_id=(W, njmax), efc_state=(W, njmax), efc_J=(W, njmax_pad, nv_pad), efc_pos=(W, njmax),
-    efc_margin=(W, njmax), efc_D=(W, njmax), efc_vel=(W, njmax), efc_aref=(W, njmax), efc_frictionloss=(W, njmax),
-    efc_force=(W, njmax), ws_ncon=(W,), ws_conadr=(W,), ws_ncollision=(W,), ws_efc_con=(W, njmax), ws_tree_rowadr=(W, (m.ntree + 1) if m.tree_solve else 0), ws_tree_rowmap=(W, njmax if m.tree_solve else 0),
-    ws_isl_dofadr=(W, (m.ntree + 1) if m.tree_solve else 0), ws_isl_dofmap=(W, nv if m.tree_solve else 0), ws_isl_dofinv=(W, nv if m.tree_solve else 0), ws_nisland=(W,), ws_isl_flags=(W,), ws_isl_list=(3, W if m.tree_solve else 0), ws_isl_count=(4,),
-    ws_separable=(W,), ws_order=(W,), ws_ccd=(W if m._convex_pairs else 0, _ccd_words(W, max(int(m.opt.ccd_iterations), int(m.epa_iterations)), m.nhfield, m.npolygonmax, m.nmeshdegmax, _collide_ccap(int(m.npair), contact_cap(nconmax)), int(m.npair), handcap), 32),
-    tree_asleep=(W, m.ntree), tree_awake=(W, m.ntree), body_awake=(W, nb), body_awake_ind=(W, nb), dof_awake_ind=(W, nv), ntree_awake=(W,), nbody_awake=(W,),
-    nv_awake=(W,), tree_island=(W, m.ntree), nisland=(W,), ws_iacc=(W if int(m.opt.integrator) == int(types.IntegratorType.IMPLICIT) else 0, nv), ws_pgsB=(W if _needs_pgs_big(m) else 0, njmax_pad, nv_pad), ws_sleep_J=(W if m.sleep_enabled else 0, njmax_pad, nv_pad), ws_sleep_warm=(W if m.sleep_enabled else 0, nv),
-    ws_sleep_flag=(W,),
-    sensordata=(W, m.nsensordata), energy=(W, 2), subtree_linvel=(W, nb, 3), subtree_angmom=(W, nb, 3), cfrc_ext=(W, nb, 6), eq_active=(W, m.neq), ws_rk=(W, nq + 3 * nv + 2 * na), ws_contact=(W, contact_cap(nconmax), 32),
-  )
-  return sh, njmax_pad, nv_pad
-
-
 def _needs_pgs_big(m: types.Model) -> bool:
   """PGS with more than 64 dofs or elliptic cones runs the generic kernel (csrc/pgs_big.hpp), which keeps J M^-1 in Data.ws_pgsB."""
   return int(m.opt.solver) == int(types.SolverType.PGS) and (m.nv > 64 or int(m.opt.cone) == int(types.ConeType.ELLIPTIC))
+
+
+def _data_sizes(m: types.Model, nworld, nconmax, njmax, naconmax, handcap=None):
+  """Every size the shapes of types.Data / Contact / Constraint name, for a Data of `m` with these capacities.  Workspaces of a kernel
+  family the model does not run have a leading size of 0."""
+  sizes = {name: int(getattr(m, name)) for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nmocap", "neq", "nC", "ntree", "nsensordata", "nmaxpyramid")}
+  sizes["njmax_pad"], sizes["nv_pad"] = _get_padded_sizes(m.nv, njmax)
+  concap, tree = contact_cap(nconmax), bool(m.tree_solve)
+  sizes.update(
+    nworld=nworld, njmax=njmax, naconmax=naconmax, concap=concap,
+    ntreeadr=m.ntree + 1 if tree else 0, ntreerow=njmax if tree else 0, ntreedof=m.nv if tree else 0, ntreeworld=nworld if tree else 0,
+    nsleepworld=nworld if m.sleep_enabled else 0, npgsworld=nworld if _needs_pgs_big(m) else 0,
+    nimpworld=nworld if int(m.opt.integrator) == int(types.IntegratorType.IMPLICIT) else 0, nccdworld=nworld if m._convex_pairs else 0,
+    nccdword=_ccd_words(nworld, max(int(m.opt.ccd_iterations), int(m.epa_iterations)), m.nhfield, m.npolygonmax, m.nmeshdegmax,
+                        _collide_ccap(int(m.npair), concap), int(m.npair), handcap))
+  return sizes
 
 
 def _alloc_data(m: types.Model, nworld, nconmax, njmax, naconmax, mjd=None, nvmax=None, nccdmax=None, naccdmax=None):
@@ -735,31 +718,28 @@ def _alloc_data(m: types.Model, nworld, nconmax, njmax, naconmax, mjd=None, nvma
   handcap = None
   if m._convex_pairs and (naccdmax is not None or nccdmax is not None):
     handcap = max(int(naccdmax) if naccdmax is not None else int(nccdmax) * nworld, 1)
-  shapes, njmax_pad, nv_pad = _data_shapes(m, nworld, nconmax, njmax, naconmax, handcap)
+  sizes = _data_sizes(m, nworld, nconmax, njmax, naconmax, handcap)
   d = types.Data()
   d.contact = types.Contact()
   d.efc = types.Constraint()
   d.contact._root = d
   d.efc._root = d
-  for name, kind in _DATA_PTR_FIELDS:
-    arr = DeviceArray.zeros(shapes[name], dtype=np.int32 if kind == "int" else np.float32)
-    _set_data_field(d, name, arr)
-  d.nworld, d.nconmax, d.naconmax, d.njmax, d.njmax_pad, d.nv_pad = nworld, nconmax, naconmax, njmax, njmax_pad, nv_pad
+  for name in _DATA_PTR_FIELDS:
+    shape, dtype, _ = _DATA_ARRAYS[name]
+    _set_data_field(d, name, DeviceArray.zeros(types.eval_shape(shape, sizes), dtype=dtype))
+  for name in ("nworld", "naconmax", "njmax", "njmax_pad", "nv_pad", "nsleepworld", "npgsworld", "nimpworld", "nccdworld", "nccdword", "concap"):
+    setattr(d, name, sizes[name])
+  d.nconmax = nconmax
   d.ws_order.assign(np.arange(nworld, dtype=np.int32))
   d.sleep_pass = 0
   d.nvmax = int(nvmax)
-  d.nsleepworld = shapes["ws_sleep_J"][0]
-  d.npgsworld = shapes["ws_pgsB"][0]
-  d.nimpworld = shapes["ws_iacc"][0]
   _reset_sleep(m, d, None)
   if m.neq:
     d.eq_active.assign(np.tile(m.eq_active0, (nworld, 1)))
   _reset_mocap(m, d, None)
   d.nmaxpyramid = m.nmaxpyramid
-  d.nccdworld, d.nccdword = shapes["ws_ccd"][0], shapes["ws_ccd"][1]
   d.world_offset = 0
-  d.concap = contact_cap(nconmax)
-  d.nccdhand = (handcap if handcap is not None else _ccd_handcap(nworld, _collide_ccap(int(m.npair), d.concap))) if shapes["ws_ccd"][0] else 0
+  d.nccdhand = (handcap if handcap is not None else _ccd_handcap(nworld, _collide_ccap(int(m.npair), d.concap))) if d.nccdworld else 0
   d.njmax_nnz = njmax * m.nv
   d._c = None
   d._dirty = True

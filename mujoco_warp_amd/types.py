@@ -245,6 +245,18 @@ def _arr(shape, dtype, host=False):
   return dataclasses.field(default=None, repr=False, metadata={"shape": tuple(shape), "dtype": dtype, "host": host})
 
 
+def array_fields(cls):
+  """{name: (shape, dtype, host)} of the arrays `cls` declares through _arr: the one statement of their shapes and dtypes (io.put_model and
+  io.make_data build and allocate from it)."""
+  return {f.name: (f.metadata["shape"], f.metadata["dtype"], f.metadata["host"]) for f in dataclasses.fields(cls) if "shape" in f.metadata}
+
+
+def eval_shape(shape, sizes):
+  """The declared `shape` as a tuple of ints: its size names and expressions evaluated against the dict `sizes` (the strings are constants of
+  this module; no builtins are in reach).  '*' is passed through for the caller to resolve."""
+  return tuple(s if s == "*" or not isinstance(s, str) else int(eval(s, {"__builtins__": {}}, sizes)) for s in shape)
+
+
 class _Dirty:
   """Attribute container that remembers when a field was re-bound (so the C struct is rebuilt lazily)."""
 
@@ -454,9 +466,8 @@ class Model(_Dirty):
   mesh_vertadr: DeviceArray = _arr(('nmesh',), "int32")
   mesh_vertnum: DeviceArray = _arr(('nmesh',), "int32")
   mesh_vert: DeviceArray = _arr(('nmeshvert', 3), "float32")
-  # triangles of the meshes, for rays (reference types.py Model.mesh_face / mesh_faceadr / nmeshface): mesh_face is [nmeshface, 3] int32, vertex ids
-  # local to the mesh's vertex block (declared without a symbolic shape: nmeshface is not among the sizes the schema check evaluates)
-  mesh_face: DeviceArray = dataclasses.field(default=None, repr=False, metadata={"dtype": "int32", "host": False})
+  # triangles of the meshes, for rays (reference types.py Model.mesh_face / mesh_faceadr / nmeshface): vertex ids local to the mesh's vertex block
+  mesh_face: DeviceArray = _arr(('nmeshface', 3), "int32")
   mesh_faceadr: DeviceArray = _arr(('nmesh',), "int32")
   nmeshface: int = 0
   nmeshvert: int = 0

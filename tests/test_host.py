@@ -362,19 +362,21 @@ def _schema_check(obj, env, nworld):
     assert tuple(v.shape) == tuple(want), (type(obj).__name__, name, v.shape, want)
 
 
-@pytest.mark.parametrize("xml", ["humanoid", "panda", "pendula"])
+@pytest.mark.parametrize("xml", ["humanoid", "panda", "pendula", "clutter"])
 def test_declared_schema_matches_arrays(xml):
   """types.Model / Data / Option / Contact / Constraint are real dataclasses: every attribute put_model / make_data sets is a
   declared field and every declared array has the declared (symbolic) shape and dtype."""
   import dataclasses
 
   mjm = {"humanoid": lambda: mjw.mjcf.load_xml(conftest.HUMANOID_XML), "panda": lambda: mjw.mjcf.load_xml(conftest.PANDA_XML),
-         "pendula": lambda: mjw.mjcf.from_xml_string(conftest.PENDULA_XML)}[xml]()
+         "pendula": lambda: mjw.mjcf.from_xml_string(conftest.PENDULA_XML),
+         "clutter": lambda: mjw.mjcf.load_xml(os.path.join(conftest.ROOT, "benchmarks", "clutter_synth", "scene_clutter_synth.xml"))}[xml]()
   m = mjw.put_model(mjm)
+  assert xml != "clutter" or m.nmeshface > 0  # (the mesh scene: Model.mesh_face's declared shape meets a non-empty array)
   d = mjw.make_data(mjm, nworld=3, nconmax=7, njmax=21)
   assert dataclasses.is_dataclass(mjw.Model) and dataclasses.is_dataclass(mjw.Data)
   env = {k: getattr(m, k) for k in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nkey", "nmocap", "neq", "nC", "npair", "ncullgeom", "ncullgroup", "ncullpair",
-                                    "nexplicit", "nbodylevel", "ndoflevel", "nmaxpyramid", "ntree", "nmesh", "nmeshvert", "nmeshpoly", "nmeshpolyvert", "nmeshpolymap", "nmeshgraph", "nhfield", "nhfielddata", "nsensor", "nsensordata", "nmat")}
+                                    "nexplicit", "nbodylevel", "ndoflevel", "nmaxpyramid", "ntree", "nmesh", "nmeshvert", "nmeshface", "nmeshpoly", "nmeshpolyvert", "nmeshpolymap", "nmeshgraph", "nhfield", "nhfielddata", "nsensor", "nsensordata", "nmat")}
   env.update(nworld=d.nworld, njmax=d.njmax, njmax_pad=d.njmax_pad, nv_pad=d.nv_pad, naconmax=d.naconmax, concap=d.concap, nccdworld=d.nccdworld, nccdword=d.nccdword, ntreeadr=(m.ntree + 1) if m.tree_solve else 0, ntreerow=d.njmax if m.tree_solve else 0, ntreedof=m.nv if m.tree_solve else 0, ntreeworld=d.nworld if m.tree_solve else 0, nsleepworld=d.nsleepworld, npgsworld=d.npgsworld, nimpworld=d.nimpworld)
   for obj in (m.opt, m.stat, m, d.contact, d.efc, d):
     _schema_check(obj, env, d.nworld)
