@@ -346,12 +346,41 @@ int mjh_qld_dense(const MjhModel* m, const MjhData* d, float* qld_dense, int str
 int mjh_contact_force(const MjhModel* m, const MjhData* d, const int* contact_ids, int n, int to_world_frame, float* force, void* stream);
 /* support.jac (support.py:581): Jacobians [nworld, 3, nv] of point[w] (world coordinates) moving with body[w]; jacp or jacr may be NULL */
 int mjh_jac(const MjhModel* m, const MjhData* d, float* jacp, float* jacr, const float* point, const int* body, void* stream);
-/* ray.rays (ray.py:1219): nearest intersection of nray rays per world with the primitive geoms (mesh / height-field geoms are not
-   intersected).  pnt, vec [pnt_nworld (1 or nworld), nray, 3] device; geomgroup: 6 host floats (NULL or six -1: every group; otherwise
+/* ray.rays (ray.py:1219): nearest intersection of nray rays per world with the geoms (primitives, meshes, height fields).  pnt, vec [pnt_nworld (1 or nworld), nray, 3] device; geomgroup: 6 host floats (NULL or six -1: every group; otherwise
    groups whose entry is 0 are skipped); bodyexclude [nray] device ints or NULL; dist [nworld, nray] (-1: no hit); geomid, normal may be NULL */
 int mjh_rays(const MjhModel* m, const MjhData* d, const float* pnt, const float* vec, int pnt_nworld, int nray, const float* geomgroup,
              int flg_static, const int* bodyexclude, float* dist, int* geomid, float* normal, void* stream);
 int mjh_efc_j_sparse(const MjhModel* m, const MjhData* d, int njmax_nnz, int* rownnz, int* rowadr, int* colind, float* values, void* stream);
+
+/* Render context of the depth / segmentation cameras (mujoco_warp_amd/render.py create_render_context; csrc/render.hpp).  The camera tables live
+   here, not in MjhModel.  Pixels of all cameras share one flat axis of npixel entries: camera c owns [depth_adr[c], depth_adr[c] + w h), row 0 on
+   top.  An image is cut into 8 x 8 pixel tiles, listed in `tile`. */
+typedef struct MjhRender {
+  int nworld;                   /* worlds the output buffers were allocated for (must equal MjhData.nworld)                     */
+  int ncam;                     /* active cameras                                                                                */
+  int npixel;                   /* pixels of all active cameras                                                                  */
+  int ntile;                    /* 8 x 8 tiles of all active cameras                                                             */
+  int groupmask;                /* bit g set: geoms of group g (clamped to 0..5) are rendered                                    */
+  const int* cam_bodyid;        /* [ncam] body a camera rides on                                                                 */
+  const float* cam_pos;         /* [ncam, 3] position in the body frame                                                          */
+  const float* cam_quat;        /* [ncam, 4] orientation in the body frame (unit; the camera looks along -z, +y is up)           */
+  const int* cam_res;           /* [ncam, 2] width, height                                                                       */
+  const int* cam_exclude;       /* [ncam] body whose geoms the camera does not see (-1: none)                                    */
+  const int* depth_adr;         /* [ncam] first pixel of a camera in depth / normal                                              */
+  const int* seg_adr;           /* [ncam] first pixel of a camera in seg                                                         */
+  const int* tile;              /* [ntile, 3] camera, x and y of the tile's first pixel                                          */
+  const float* ray;             /* [npixel, 3] unit pixel directions in the camera frame                                         */
+  float* depth;                 /* [nworld, npixel] planar depth (0: nothing hit)                                                */
+  int* seg;                     /* [nworld, npixel, 2] (geom id, mjOBJ_GEOM = 5) or (-1, -1); may be NULL                        */
+  float* normal;                /* [nworld, npixel, 3] world-frame surface normal; may be NULL                                   */
+  float* cam_xpos;              /* [nworld, ncam, 3] camera positions of the last render / camera_rays call                      */
+  float* cam_xmat;              /* [nworld, ncam, 9] camera orientations                                                         */
+} MjhRender;
+/* render: fills rc->cam_xpos / cam_xmat from Data.xpos / xmat and depth / seg / normal from Data.geom_xpos / geom_xmat (kinematics must have
+   run): per pixel the hit mjh_rays would report for the pixel's ray with rc's group mask, flg_static = 1 and bodyexclude = cam_exclude. */
+int mjh_render(const MjhModel* m, const MjhData* d, const MjhRender* rc, void* stream);
+/* world-frame origin and direction [nworld, npixel, 3] of every pixel ray of rc (also refreshes rc->cam_xpos / cam_xmat) */
+int mjh_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc, float* pnt, float* vec, void* stream);
 
 /* cli._ctrl_noise cli.py:103-145; ctrl_center may be NULL (-> actuator midpoint); worldid is global */
 int mjh_ctrl_noise(const MjhModel* m, const MjhData* d, const float* ctrl_center, int step, float noise_std,
@@ -387,7 +416,7 @@ int mjh_dev_knob(const char* name, const char* value);
  * wavefront), "pair" (k_solve<cg>), "newton_mfma", "newton32", "cg64", "newton64", "*_ell", "tree+big", "big", "pgs", "pgs_big", "unsupported" -- so that a
  * test or a bench line can say which kernel it measured without a knob.  Static string; host only; launches nothing. */
 const char* mjh_solver_kernel(const MjhModel* m, const MjhData* d);
-#define MJH_ABI_VERSION 44
+#define MJH_ABI_VERSION 45
 /* floats of Data.ws_ccd for a model with GJK pairs (csrc/convex.hpp ccd_layout: per world the candidate list, the per-candidate result cache and the
    broadphase mask; then the counters, the convex-pair mask and the EPA hand-over records) -- what a binding that allocates Data itself must
    provide; iterations = max(ccd_iterations, epa_iterations), concap = Data.concap.  Also returns the default Data.nccdhand through *nccdhand_out

@@ -7,7 +7,8 @@
 //   one-row-per-lane solve_ell_newton32_r1.hip       k_solve_plus instantiations (solve_newton32.hip also k_solve_newton, MFMA)
 //   solve_cgp.hip / solve_cgw.hip      k_solve_cgp_plus (pooled contact-basis CG) / k_solve_cgw_plus (one world per wavefront)
 //   solve_tree_cg / solve_tree_newton / solve_tree_ell_cg / solve_tree_ell_newton .hip   k_solve_tree (per-island solves, nv > 64)
-//   pgs_tu.hip (k_solve_pgs, k_solve_pgs_big), solve_big.hip (k_solve_big), build_id.hip (the source hash, no kernels)
+//   pgs_tu.hip (k_solve_pgs, k_solve_pgs_big), solve_big.hip (k_solve_big), render_tu.hip (k_render, k_camera_rays: the cameras),
+//   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -160,3 +161,6 @@ int launch_pgs(const MjhModel* m, const MjhData* d, hipStream_t s);
 int launch_pgs_big(const MjhModel* m, const MjhData* d, hipStream_t s);
 // generic LDS solver (solver_big.hpp): nv > 64, and the worlds of a small model with more than nefc_lo = 192 rows
 int launch_solve_big(const MjhModel* m, const MjhData* d, hipStream_t s, int nefc_lo = -1);
+// cameras (render.hpp, render_tu.hip): camera frames + the tile kernel / the pixel rays in the world frame; mjhip.hip checks the arguments
+int launch_render(const MjhModel* m, const MjhData* d, const MjhRender* rc, hipStream_t s);
+int launch_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc, float* pnt, float* vec, hipStream_t s);

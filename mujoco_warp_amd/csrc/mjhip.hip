@@ -1050,6 +1050,34 @@ int mjh_rays(const MjhModel* m, const MjhData* d, const float* pnt, const float*
   return MJH_OK;
 }
 
+// the cameras (csrc/render.hpp; the kernels are render_tu.hip's)
+static int check_render(const char* who, const MjhModel* m, const MjhData* d, const MjhRender* rc) {
+  if (!rc) return fail(MJH_E_ARG, "%s: null render context", who);
+  if (rc->nworld != d->nworld) return fail(MJH_E_ARG, "%s: the render context was built for another nworld", who);
+  if (rc->ncam < 0 || rc->npixel < 0 || rc->ntile < 0) return fail(MJH_E_ARG, "%s: negative size in the render context", who);
+  if (rc->ncam == 0 || rc->npixel == 0) return MJH_OK;
+  if (!rc->cam_bodyid || !rc->cam_pos || !rc->cam_quat || !rc->cam_res || !rc->cam_exclude || !rc->depth_adr || !rc->seg_adr || !rc->tile || !rc->ray || !rc->cam_xpos || !rc->cam_xmat)
+    return fail(MJH_E_ARG, "%s: null table in the render context", who);
+  if (rc->ntile == 0 || (long long)rc->ntile * 64 < rc->npixel) return fail(MJH_E_ARG, "%s: the tile table does not cover the pixels", who);
+  if ((long long)d->nworld * rc->npixel > 0x7fffffffLL) return fail(MJH_E_ARG, "%s: nworld * npixel exceeds 2^31 - 1 (render fewer worlds or cameras per context)", who);
+  if (!d->xpos || !d->xmat || !d->geom_xpos || !d->geom_xmat || (m->ngeom > 0 && !m->geom_rbound)) return fail(MJH_E_ARG, "%s: Data.xpos / xmat / geom_xpos / geom_xmat or Model.geom_rbound missing", who);
+  return MJH_OK;
+}
+int mjh_render(const MjhModel* m, const MjhData* d, const MjhRender* rc, void* stream) {
+  TRY(check(m, d));
+  TRY(check_render("mjh_render", m, d, rc));
+  if (rc->ncam == 0 || rc->npixel == 0) return MJH_OK;
+  if (!rc->depth && !rc->seg && !rc->normal) return fail(MJH_E_ARG, "mjh_render: no output buffer (depth, seg and normal are all null)");
+  return launch_render(m, d, rc, (hipStream_t)stream);
+}
+int mjh_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc, float* pnt, float* vec, void* stream) {
+  TRY(check(m, d));
+  TRY(check_render("mjh_camera_rays", m, d, rc));
+  if (rc->ncam == 0 || rc->npixel == 0) return MJH_OK;
+  if (!pnt || !vec) return fail(MJH_E_ARG, "mjh_camera_rays: null pnt / vec");
+  return launch_camera_rays(m, d, rc, pnt, vec, (hipStream_t)stream);
+}
+
 int mjh_efc_j_sparse(const MjhModel* m, const MjhData* d, int njmax_nnz, int* rownnz, int* rowadr, int* colind, float* values, void* stream) {
   TRY(check(m, d));
   if (njmax_nnz < 0 || !rownnz || !rowadr || (njmax_nnz > 0 && (!colind || !values))) return fail(MJH_E_ARG, "mjh_efc_j_sparse: null output or negative njmax_nnz");

@@ -5,7 +5,7 @@
 // over the triangles of every mesh that survives the box cull and over the cells of every height field; one lexicographic
 // (distance, geom, triangle) min-reduction picks the winner the serial walk (ray_world_full, the rangefinder's path) would pick.
 // Models whose meshes have few triangles each: one thread per (world, ray) over that serial walk (k_rays_serial_full), which measured faster there.
-// No BVH / render context.
+// No BVH; the cameras (render.hpp) cast their pixel rays with the device functions below.
 #pragma once
 #include "dev_common.hpp"
 
@@ -389,6 +389,7 @@ DEV float ray_world(const MjhModel& m, const MjhData& d, int w, V3 pnt, V3 vec, 
   }
   return best >= MJ_MAXVAL ? -1.0f : best;
 }
+#ifndef MJH_RAY_NO_KERNELS  // (render_tu.hip takes the device functions only: a kernel is defined in one translation unit)
 // rays (ray.py:1219-1325): pnt / vec [pnt_nworld (1 or nworld), nray, 3]; bodyexclude [nray]; outputs [nworld, nray]
 __global__ void __launch_bounds__(256) k_rays(MjhModel m, MjhData d, const float* pnt, const float* vec, int pnt_nworld, int nray, RayGroup gg, int flg_static,
                                               const int* bodyexclude, float* dist, int* geomid, float* normal) {
@@ -403,6 +404,7 @@ __global__ void __launch_bounds__(256) k_rays(MjhModel m, MjhData d, const float
   if (geomid) geomid[idx] = g;
   if (normal) st3(normal + (size_t)idx * 3, n);
 }
+#endif
 
 // ---- models with mesh triangles or height fields ----
 // lanes of a (world, ray) group in k_rays_group (one DPP row: the closing reduction stays inside a row) and the model size from which the group
@@ -442,6 +444,7 @@ DEV float ray_world_full(const MjhModel& m, const MjhData& d, int w, V3 pnt, V3 
   normal = h.n;
   return h.dist >= MJ_MAXVAL ? -1.0f : h.dist;
 }
+#ifndef MJH_RAY_NO_KERNELS
 // rays() on a model with large meshes or a height field: G = RAY_LANES lanes per (world, ray).  Groups are numbered ray-major (group q: world q % nworld, ray q / nworld), so the
 // 256 / G groups of a workgroup cast the same ray in neighbouring worlds: with a broadcast pnt / vec, and for static geoms in any case, they
 // walk the same model-constant triangles, which the workgroup then fetches once into its L1 / from L2 instead of once per world.
@@ -510,3 +513,4 @@ __global__ void __launch_bounds__(256) k_rays_serial_full(MjhModel m, MjhData d,
   if (geomid) geomid[idx] = g;
   if (normal) st3(normal + (size_t)idx * 3, n);
 }
+#endif  // MJH_RAY_NO_KERNELS

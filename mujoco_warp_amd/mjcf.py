@@ -93,6 +93,23 @@ class MjStatistic:
     self.center = np.zeros(3)
 
 
+class MjCamera:
+  """The <camera> elements of a model, in body order: poses in the body frame (the camera looks along -z, +y is up), vertical field of
+  view in degrees, resolution (width, height).  `unbuilt[i]` lists the (attribute, value) pairs of camera i that create_render_context
+  does not render (tracking / targeting modes, orthographic projection, explicit intrinsics)."""
+
+  def __init__(self, cams=()):
+    self.n = len(cams)
+    self.names = [c["name"] for c in cams]
+    self.bodyid = np.array([c["body"] for c in cams], dtype=np.int32)
+    self.pos = np.array([c["pos"] for c in cams], dtype=np.float64).reshape(-1, 3)
+    self.quat = np.array([c["quat"] for c in cams], dtype=np.float64).reshape(-1, 4)
+    self.fovy = np.array([c["fovy"] for c in cams], dtype=np.float64)
+    self.resolution = np.array([c["resolution"] for c in cams], dtype=np.int32).reshape(-1, 2)
+    self.mode = [c["mode"] for c in cams]
+    self.unbuilt = [list(c["unbuilt"]) for c in cams]
+
+
 class MjModel:
   """numpy stand-in for mujoco.MjModel (only fields on the mj_step hot path)."""
 
@@ -332,8 +349,8 @@ def _compiler_of(root):
 
 def _place(elem, fpos, fquat, comp):
   """Re-express a posed child of a frame in the frame's parent: p' = fpos + R(fquat) p, q' = fquat * q."""
-  if elem.tag not in ("body", "geom", "site"):
-    return  # cameras and lights do not enter the dynamics
+  if elem.tag not in ("body", "geom", "site", "camera"):
+    return  # lights do not enter the engine
   a = elem.attrib
   if "fromto" in a:
     ft = _floats(a["fromto"])
@@ -383,7 +400,7 @@ class _Structure:
           _place(c, fpos, fquat, self.comp)
           if cc is not None:
             key = "childclass" if c.tag == "body" else "class"
-            if c.tag in ("body", "geom", "site", "joint") and key not in c.attrib:
+            if c.tag in ("body", "geom", "site", "joint", "camera") and key not in c.attrib:
               c.set(key, cc)
           out.append(c)
       elif child.tag == "replicate":
@@ -815,7 +832,7 @@ def _compile(root, base_dir):
       mat_names.append(a.get("name", ""))
       mat_rgba.append(_vec(a, "rgba", [1.0, 1.0, 1.0, 1.0]))
 
-  bodies, joints, geoms, sites = [], [], [], []
+  bodies, joints, geoms, sites, cameras = [], [], [], [], []
   world = _Body()
   world.name, world.parent, world.pos, world.quat = "world", 0, np.zeros(3), np.array([1.0, 0, 0, 0])
   world.inertial, world.joints, world.geoms, world.gravcomp, world.mocap = None, [], [], 0.0, False
@@ -969,6 +986,18 @@ def _compile(root, base_dir):
       j["limited"] = False
     return j
 
+  def parse_camera(elem, childclass, bodyid):
+    base, explicit = _resolve("camera", elem, table, childclass)
+    a = dict(base)
+    a.update(explicit)
+    res = _vec(a, "resolution", [1, 1])
+    # what create_render_context cannot render (render.py refuses the camera when it is active): (attribute, value) pairs
+    unbuilt = [("mode", a["mode"])] if a.get("mode", "fixed") != "fixed" else []
+    unbuilt += [("orthographic", "true")] if _bool(a.get("orthographic", "false")) else []
+    unbuilt += [(k, a[k]) for k in ("sensorsize", "focal", "focalpixel", "principal", "principalpixel") if k in a]
+    cameras.append({"name": a.get("name", ""), "body": bodyid, "pos": _vec(a, "pos", [0, 0, 0]), "quat": _orientation(a, compiler),
+                    "fovy": float(a.get("fovy", 45.0)), "resolution": [int(res[0]), int(res[1])], "mode": a.get("mode", "fixed"), "unbuilt": unbuilt})
+
   def parse_body(elem, parentid, childclass):
     b = _Body()
     cc = elem.get("childclass", childclass)
@@ -1016,7 +1045,9 @@ def _compile(root, base_dir):
         a.update(explicit)
         sites.append({"name": a.get("name", ""), "body": bid, "pos": _vec(a, "pos", [0, 0, 0]),
                       "quat": _orientation(a, compiler), "size": _site_size(a), "type": _GEOM_NAMES[a.get("type", "sphere")]})
-      elif child.tag not in ("camera", "light", "body"):
+      elif child.tag == "camera":
+        parse_camera(child, cc, bid)
+      elif child.tag not in ("light", "body"):
         # <frame>, <replicate>, <attach>, <composite>, <flexcomp>, <plugin>, ...: never skipped silently
         raise NotImplementedError(f"<{child.tag}> inside <body>")
     for child in elem:
@@ -1038,6 +1069,8 @@ def _compile(root, base_dir):
       a.update(explicit)
       sites.append({"name": a.get("name", ""), "body": 0, "pos": _vec(a, "pos", [0, 0, 0]),
                     "quat": _orientation(a, compiler), "size": _site_size(a), "type": _GEOM_NAMES[a.get("type", "sphere")]})
+    elif child.tag == "camera":
+      parse_camera(child, None, 0)
   for child in wb:
     if child.tag == "body":
       parse_body(child, 0, None)
@@ -1522,6 +1555,8 @@ def _compile(root, base_dir):
   # sizes not on the hot path
   m.ntendon = m.nflex = m.nplugin = 0
   m.ncam = m.nlight = 0
+  # cameras: a record beside the model, not Model fields (ncam stays 0: nothing of the step reads a camera); render.py consumes it
+  m.camera = MjCamera(cameras)
   m.nuserdata = 0
   _compile_sensors(m, root, [s_["name"] for s_ in sites])
 

@@ -5,7 +5,7 @@ primitive-only one the one-thread-per-ray kernel -- the model decides.  A visibl
 loader reads a mesh asset only for colliding or mass-carrying geoms, so the visual-only shells of aloha_pot and Unitree G1 (geom group 2) are
 such geoms: `rays()` raises NotImplementedError unless the call's `geomgroup` hides every group they are in (rays are then cast against the
 collision geometry), and `put_model` raises for a rangefinder sensor (which has no group mask) -- never a silent "no hit" (the reference's ray
-elimination, ray.py:52, keeps the geom); there is no BVH / render context."""
+elimination, ray.py:52, keeps the geom); there is no BVH.  Depth / segmentation cameras: render.py."""
 
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -27,7 +27,7 @@ def rays(m, d, pnt: DeviceArray, vec: DeviceArray, geomgroup: Optional[Sequence[
   flg_static: whether geoms of static bodies can be hit.  bodyexclude: [nray] int32 body whose geoms each ray ignores (-1: none), or None.
   dist [nworld, nray] (-1: no hit), geomid [nworld, nray] (-1), normal [nworld, nray, 3] are written; geomid / normal may be None."""
   if rc is not None:
-    raise NotImplementedError("render contexts (BVH-accelerated mesh / flex rays) are not part of this engine")
+    raise NotImplementedError("rays(rc=...): BVH render contexts are not part of this engine; a RenderContext of create_render_context serves render() and camera_rays(), whose rays can be passed here")
   if getattr(m, "_ray_unsupported_geoms", 0):
     groups = getattr(m, "_ray_unsupported_groups", list(range(6)))
     masked = geomgroup is not None and len(geomgroup) == 6 and not all(float(x) == -1 for x in geomgroup) and all(float(geomgroup[g]) == 0 for g in groups)
