@@ -891,13 +891,21 @@ DEV void collide_pair(int t1, int t2, V3 p1, const float* R1, V3 s1, V3 p2, cons
     plane_sphere(ax1, p1, p2 - seg, s2.x, dist, pos);
     emit(1, dist, pos, ax1, b, c);
   } else if (t1 == G_PLANE && t2 == G_BOX) {  // core:337
-    const float cd = dot(p2 - p1, ax1);
+#pragma clang fp contract(off)
+    // every sum of products spelled out as fused operations, nothing left to contract: a sum of two products can be fused either way round,
+    // and the light and the heavy instantiation of this function chose differently (1 ulp in dist; tests/test_colliders.py compares the
+    // instantiations bit for bit)
+    const float dx = p2.x - p1.x, dy = p2.y - p1.y, dz = p2.z - p1.z;
+    const float cd = fmaf(dz, ax1.z, fmaf(dy, ax1.y, dx * ax1.x));
     const Frame f = make_frame3(ax1);
     for (int i = 0; i < 8; ++i) {
-      V3 corner = V3{(i & 1) ? s2.x : -s2.x, (i & 2) ? s2.y : -s2.y, (i & 4) ? s2.z : -s2.z};
-      V3 cw = mat_mul(R2, corner);
-      const float cdist = cd + dot(ax1, cw);
-      emit(i, cdist, cw + p2 - ax1 * (0.5f * cdist), f.a, f.b, f.c);
+      const float cx = (i & 1) ? s2.x : -s2.x, cy = (i & 2) ? s2.y : -s2.y, cz = (i & 4) ? s2.z : -s2.z;
+      const float wx = fmaf(R2[2], cz, fmaf(R2[1], cy, R2[0] * cx));
+      const float wy = fmaf(R2[5], cz, fmaf(R2[4], cy, R2[3] * cx));
+      const float wz = fmaf(R2[8], cz, fmaf(R2[7], cy, R2[6] * cx));
+      const float cdist = cd + fmaf(ax1.z, wz, fmaf(ax1.y, wy, ax1.x * wx));
+      const float h = 0.5f * cdist;
+      emit(i, cdist, V3{fmaf(-ax1.x, h, wx + p2.x), fmaf(-ax1.y, h, wy + p2.y), fmaf(-ax1.z, h, wz + p2.z)}, f.a, f.b, f.c);
     }
   } else if (t1 == G_PLANE && t2 == G_ELLIPSOID) {  // core:306
     V3 loc = matT_mul(R2, ax1);
@@ -944,9 +952,21 @@ DEV void collide_pair(int t1, int t2, V3 p1, const float* R1, V3 s1, V3 p2, cons
     V3 axis1 = ax1 * s1.y, axis2 = ax2 * s2.y, dif = p1 - p2;
     const float ma = dot(axis1, axis1), mb = -dot(axis1, axis2), mc = dot(axis2, axis2);
     const float u = -dot(axis1, dif), v = dot(axis2, dif);
-    const float det = ma * mc - mb * mb;
-    if (fabsf(det) >= MJ_MINVAL) {
-      float x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
+    float det = ma * mc - mb * mb, num1 = mc * u - mb * v, num2 = ma * v - mb * u;
+    bool skew = fabsf(det) >= MJ_MINVAL;
+    if (fabsf(det) < 1e-5f * ma * mc) {
+      // axes within 3e-3 rad: these differences of products cancel to rounding noise in float32 (vertical capsules of different lengths:
+      // noise of either sign against MJ_MINVAL, garbage parameters, contacts lost or a centimetre off).  The same three numbers through the
+      // cross product (Lagrange's identity), which keeps its digits down to ~1e-7 rad; parallel below 1e-6 rad, far above its rounding
+      // whatever the capsules' size.  Above the threshold nothing changes.
+      const V3 cx = cross(ax1, ax2) * (s1.y * s2.y);
+      det = dot(cx, cx);
+      num1 = dot(cx, cross(axis2, dif));
+      num2 = dot(cx, cross(axis1, dif));
+      skew = det >= fmaxf(MJ_MINVAL, 1e-12f * ma * mc);
+    }
+    if (skew) {
+      float x1 = num1 / det, x2 = num2 / det;
       if (x1 > 1.0f) {
         x1 = 1.0f;
         x2 = (v - mb) / mc;

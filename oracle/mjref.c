@@ -1582,9 +1582,25 @@ static int collide_pair(const RefModel* m, RefData* d, int g1, int g2, double ma
     v3sub(dif, p1, p2);
     double ma = v3dot(axis1, axis1), mb = -v3dot(axis1, axis2), mc = v3dot(axis2, axis2);
     double u = -v3dot(axis1, dif), v = v3dot(axis2, dif);
-    double det = ma * mc - mb * mb;
-    if (fabs(det) >= MINVAL) {
-      double x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
+    double det = ma * mc - mb * mb, num1 = mc * u - mb * v, num2 = ma * v - mb * u;
+    int skew = fabs(det) >= MINVAL;
+#ifdef REF_REAL_FLOAT
+    if (fabs(det) < 1e-5f * ma * mc) {
+      /* float32 build, as csrc/collide.hpp: within 3e-3 rad of parallel these differences of products are rounding noise; the same three
+         numbers through the cross product (Lagrange's identity); parallel below 1e-6 rad.  The float64 build keeps the reference's. */
+      double cx[3], c1[3], c2[3];
+      v3cross(cx, ax1, ax2);
+      for (int k = 0; k < 3; k++) cx[k] *= s1[1] * s2[1];
+      v3cross(c1, axis2, dif);
+      v3cross(c2, axis1, dif);
+      det = v3dot(cx, cx);
+      num1 = v3dot(cx, c1);
+      num2 = v3dot(cx, c2);
+      skew = det >= fmax(MINVAL, 1e-12f * ma * mc);
+    }
+#endif
+    if (skew) {
+      double x1 = num1 / det, x2 = num2 / det;
       if (x1 > 1.0) { x1 = 1.0; x2 = (v - mb) / mc; }
       else if (x1 < -1.0) { x1 = -1.0; x2 = (v + mb) / mc; }
       if (x2 > 1.0) { x2 = 1.0; x1 = clampd((u - mb) / ma, -1.0, 1.0); }
