@@ -352,6 +352,18 @@ int mjh_rays(const MjhModel* m, const MjhData* d, const float* pnt, const float*
              int flg_static, const int* bodyexclude, float* dist, int* geomid, float* normal, void* stream);
 int mjh_efc_j_sparse(const MjhModel* m, const MjhData* d, int njmax_nnz, int* rownnz, int* rowadr, int* colind, float* values, void* stream);
 
+/* set_const (reference set_const.py; the float64 host version is mujoco_warp_amd/mjcf.py set_const): the constants derived from the inertial
+ * parameters, recomputed for nbatch model-worlds in ONE launch that touches no Data (csrc/set_const.hpp; an addition within ABI v45: no struct
+ * changed).  `what` is a mask of MJH_SET_CONST_FIXED (body_subtreemass [nbatch, nbody], from body_mass) and MJH_SET_CONST_0 (dof_invweight0
+ * [nbatch, nv], body_invweight0 [nbatch, nbody, 2], stat_meaninertia [nbatch], at qpos0); a NULL output is not requested.  World w reads row
+ * w % nb of every batched input (body_mass, body_inertia, body_ipos, body_iquat, body_pos, body_quat, jnt_pos, jnt_axis, dof_armature, qpos0:
+ * nb must be 1 or nbatch) and writes row w of the outputs -- passed as writable pointers because MjhModel declares its fields const; they
+ * may be the model's own arrays.  nv == 0: meaninertia 1, body_invweight0 0. */
+#define MJH_SET_CONST_FIXED 1
+#define MJH_SET_CONST_0 2
+int mjh_set_const(const MjhModel* m, int nbatch, float* body_subtreemass, float* dof_invweight0, float* body_invweight0, float* stat_meaninertia, int what,
+                  void* stream);
+
 /* Render context of the depth / segmentation cameras (mujoco_warp_amd/render.py create_render_context; csrc/render.hpp).  The camera tables live
    here, not in MjhModel.  Pixels of all cameras share one flat axis of npixel entries: camera c owns [depth_adr[c], depth_adr[c] + w h), row 0 on
    top.  An image is cut into 8 x 8 pixel tiles, listed in `tile`. */

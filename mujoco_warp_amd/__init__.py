@@ -1,7 +1,10 @@
 """mujoco_warp_amd: MI355X-native batched MuJoCo stepping engine behind the mujoco_warp Python API.
 
 Public surface mirrors /root/reference/mujoco_warp/__init__.py:26-123 for the mj_step hot path
-(put_model / put_data / make_data / get_data_into / reset_data / step / forward + stage functions + enums).
+(put_model / put_data / make_data / get_data_into / reset_data / step / forward + stage functions + enums), plus
+set_const / set_const_0 / set_const_fixed / set_const_spring (reference __init__.py, _src/set_const.py): the constants derived from the
+inertial parameters (body_subtreemass, dof_invweight0, body_invweight0, stat.meaninertia), recomputed on the device for every model-world
+after a domain randomisation.
 Physics runs in hand-written HIP kernels (csrc/) reached through the C ABI in include/mjhip.h.
 """
 
@@ -75,6 +78,10 @@ from .io import put_data
 from .io import put_model
 from .io import reset_data
 from .io import reset_data_keyframe
+from .set_const import set_const
+from .set_const import set_const_0
+from .set_const import set_const_fixed
+from .set_const import set_const_spring
 from .mjcf import MjData
 from .mjcf import MjModel
 from .mjcf import mj_resetDataKeyframe

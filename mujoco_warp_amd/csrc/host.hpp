@@ -8,6 +8,7 @@
 //   solve_cgp.hip / solve_cgw.hip      k_solve_cgp_plus (pooled contact-basis CG) / k_solve_cgw_plus (one world per wavefront)
 //   solve_tree_cg / solve_tree_newton / solve_tree_ell_cg / solve_tree_ell_newton .hip   k_solve_tree (per-island solves, nv > 64)
 //   pgs_tu.hip (k_solve_pgs, k_solve_pgs_big), solve_big.hip (k_solve_big), render_tu.hip (k_render, k_camera_rays: the cameras),
+//   set_const_tu.hip (k_set_const and its entry point mjh_set_const: the derived model constants),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once

@@ -359,6 +359,182 @@ __host__ __device__ inline int pos_shared_words(int nv, int nC, int nbody, int n
 
 enum { POS_KINEMATICS = 0, POS_COM = 1, POS_CRB = 2, POS_FACTOR = 3 };
 
+// ---- the position stages on one world's LDS slice, model constants through pointers (a staged table or the world's row of a batched
+// field).  fwd_pos_impl below runs them on Data's qpos; k_set_const (set_const.hpp) runs them at qpos0. -------------------------------
+
+// kinematics level loop (smooth.py:46-226) over the model arrays, the lanes striding the bodies of a level.  mocap_pos / mocap_quat: the
+// world's rows of Data.mocap_*, read when use_mocap (mocap bodies otherwise keep their model pose).
+template <int G>
+DEV void kin_levels(const MjhModel& m, bool use_mocap, const float* mocap_pos, const float* mocap_quat, const float* qpos, const float* qpos0,
+                    const float* body_pos, const float* body_quat, const float* jnt_pos, const float* jnt_axis, float* xpos, float* xquat,
+                    float* xanchor, float* xaxis, int lig) {
+  for (int l = 0; l < m.nbodylevel; ++l) {
+    const int beg = m.body_leveladr[l], end = m.body_leveladr[l + 1];
+    for (int idx = beg + lig; idx < end; idx += G) {
+      const int b = m.body_tree[idx];
+      if (b == 0) {
+        st3(xpos, V3{0, 0, 0});
+        st4(xquat, Q4{1, 0, 0, 0});
+        continue;
+      }
+      const int pid = m.body_parentid[b], jntadr = m.body_jntadr[b], jntnum = m.body_jntnum[b];
+      if (jntnum == 1 && m.jnt_type[jntadr] == JNT_FREE) {
+        const int qa = m.jnt_qposadr[jntadr];
+        V3 p = ld3(qpos + qa);
+        Q4 q = quat_normalize(ld4(qpos + qa + 3));
+        st3(xpos + 3 * b, p);
+        st4(xquat + 4 * b, q);
+        st3(xanchor + 3 * jntadr, p);
+        st3(xaxis + 3 * jntadr, ld3(jnt_axis + 3 * jntadr));
+        continue;
+      }
+      Q4 pq = ld4(xquat + 4 * pid);
+      // mocap bodies (children of the world without joints) take their pose from Data.mocap_* (smooth.py:104-108)
+      const int mid = use_mocap && m.nmocap ? m.body_mocapid[b] : -1;
+      const V3 bp = mid >= 0 ? ld3(mocap_pos + (size_t)mid * 3) : ld3(body_pos + 3 * b);
+      const Q4 bq = mid >= 0 ? ld4(mocap_quat + (size_t)mid * 4) : ld4(body_quat + 4 * b);
+      V3 pos = rot_vec_quat(bp, pq) + ld3(xpos + 3 * pid);
+      Q4 quat = mul_quat(pq, bq);
+      for (int j = jntadr; j < jntadr + jntnum; ++j) {
+        const int qa = m.jnt_qposadr[j], t = m.jnt_type[j];
+        V3 jp = ld3(jnt_pos + 3 * j), ja = ld3(jnt_axis + 3 * j);
+        V3 anchor = rot_vec_quat(jp, quat) + pos;
+        V3 axis = rot_vec_quat(ja, quat);
+        if (t == JNT_BALL) {
+          quat = mul_quat(quat, quat_normalize(ld4(qpos + qa)));
+          pos = anchor - rot_vec_quat(jp, quat);
+        } else if (t == JNT_SLIDE) {
+          pos = pos + axis * (qpos[qa] - qpos0[qa]);
+        } else if (t == JNT_HINGE) {
+          quat = mul_quat(quat, axis_angle_to_quat(ja, qpos[qa] - qpos0[qa]));
+          pos = anchor - rot_vec_quat(jp, quat);
+        }
+        st3(xanchor + 3 * j, anchor);
+        st3(xaxis + 3 * j, axis);
+      }
+      st3(xpos + 3 * b, pos);
+      st4(xquat + 4 * b, quat_normalize(quat));
+    }
+    gsync();
+  }
+}
+
+// body frames: xmat, and the inertial frames xipos / ximat (no fence: the caller syncs before another lane reads them)
+template <int G>
+DEV void body_frames(int nbody, const float* body_ipos, const float* body_iquat, const float* xpos, const float* xquat, float* xmat, float* xipos,
+                     float* ximat, int lig) {
+  for (int b = lig; b < nbody; b += G) {
+    Q4 q = ld4(xquat + 4 * b);
+    quat_to_mat(q, xmat + 9 * b);
+    st3(xipos + 3 * b, ld3(xpos + 3 * b) + rot_vec_quat(ld3(body_ipos + 3 * b), q));
+    quat_to_mat(mul_quat(q, ld4(body_iquat + 4 * b)), ximat + 9 * b);
+  }
+}
+
+// com_pos (smooth.py:686-822): subtree_com, cinert, cdof; ends fenced
+template <int G>
+DEV void com_cinert_cdof(int nbody, int njnt, const float* body_mass, const float* body_subtreemass, const float* body_inertia, const int* body_subtreenum,
+                         const int* body_rootid, const int* jnt_bodyid, const int* jnt_dofadr, const int* jnt_type, const float* xmat,
+                         const float* xipos, const float* ximat, const float* xanchor, const float* xaxis, float* scom, float* cinert, float* cdof, int lig) {
+  for (int b = lig; b < nbody; b += G) {  // subtree = contiguous id range (depth-first numbering)
+    V3 s = V3{0, 0, 0};
+    const int end = b + body_subtreenum[b];
+    for (int c = b; c < end; ++c) s = s + ld3(xipos + 3 * c) * body_mass[c];
+    const float mass = body_subtreemass[b];
+    if (mass != 0.0f) s = s * (1.0f / mass);
+    st3(scom + 3 * b, s);
+  }
+  gsync();
+  for (int b = lig; b < nbody; b += G) {  // _cinert smooth.py:733
+    const float* mat = ximat + 9 * b;
+    V3 in = ld3(body_inertia + 3 * b);
+    const float mass = body_mass[b];
+    V3 dif = ld3(xipos + 3 * b) - ld3(scom + 3 * body_rootid[b]);
+    float t00 = mat[0] * in.x * mat[0] + mat[1] * in.y * mat[1] + mat[2] * in.z * mat[2];
+    float t11 = mat[3] * in.x * mat[3] + mat[4] * in.y * mat[4] + mat[5] * in.z * mat[5];
+    float t22 = mat[6] * in.x * mat[6] + mat[7] * in.y * mat[7] + mat[8] * in.z * mat[8];
+    float t01 = mat[0] * in.x * mat[3] + mat[1] * in.y * mat[4] + mat[2] * in.z * mat[5];
+    float t02 = mat[0] * in.x * mat[6] + mat[1] * in.y * mat[7] + mat[2] * in.z * mat[8];
+    float t12 = mat[3] * in.x * mat[6] + mat[4] * in.y * mat[7] + mat[5] * in.z * mat[8];
+    float* r = cinert + 10 * b;
+    r[0] = t00 + mass * (dif.y * dif.y + dif.z * dif.z);
+    r[1] = t11 + mass * (dif.x * dif.x + dif.z * dif.z);
+    r[2] = t22 + mass * (dif.x * dif.x + dif.y * dif.y);
+    r[3] = t01 - mass * dif.x * dif.y;
+    r[4] = t02 - mass * dif.x * dif.z;
+    r[5] = t12 - mass * dif.y * dif.z;
+    r[6] = mass * dif.x;
+    r[7] = mass * dif.y;
+    r[8] = mass * dif.z;
+    r[9] = mass;
+  }
+  for (int j = lig; j < njnt; j += G) {  // _cdof smooth.py:779
+    const int b = jnt_bodyid[j], t = jnt_type[j];
+    int dof = jnt_dofadr[j];
+    const float* xm = xmat + 9 * b;
+    V3 off = ld3(scom + 3 * body_rootid[b]) - ld3(xanchor + 3 * j);
+    if (t == JNT_FREE || t == JNT_BALL) {
+      if (t == JNT_FREE) {
+        for (int k = 0; k < 3; ++k) {
+          float* c = cdof + 6 * (dof + k);
+          c[0] = c[1] = c[2] = 0.0f;
+          c[3] = k == 0 ? 1.0f : 0.0f;
+          c[4] = k == 1 ? 1.0f : 0.0f;
+          c[5] = k == 2 ? 1.0f : 0.0f;
+        }
+        dof += 3;
+      }
+      for (int k = 0; k < 3; ++k) {
+        V3 ax = V3{xm[k], xm[3 + k], xm[6 + k]};
+        st3(cdof + 6 * (dof + k), ax);
+        st3(cdof + 6 * (dof + k) + 3, cross(ax, off));
+      }
+    } else if (t == JNT_SLIDE) {
+      st3(cdof + 6 * dof, V3{0, 0, 0});
+      st3(cdof + 6 * dof + 3, ld3(xaxis + 3 * j));
+    } else {
+      V3 ax = ld3(xaxis + 3 * j);
+      st3(cdof + 6 * dof, ax);
+      st3(cdof + 6 * dof + 3, cross(ax, off));
+    }
+  }
+  gsync();
+}
+
+// crb (smooth.py:1029-1098): composite inertias over the contiguous subtrees, then M in the CSR M-structure (armature on the diagonal); ends fenced
+template <int G>
+DEV void crb_mass_matrix(const MStruct& ms, int nbody, int nv, const float* armature, const int* body_subtreenum, const int* dof_bodyid,
+                         const int* dof_parentid, const float* cinert, const float* cdof, float* crb, float* M, int lig) {
+  for (int b = lig; b < nbody; b += G) {
+    float acc[10];
+    for (int k = 0; k < 10; ++k) acc[k] = cinert[10 * b + k];
+    if (b > 0) {
+      const int end = b + body_subtreenum[b];
+      for (int c = b + 1; c < end; ++c)
+        for (int k = 0; k < 10; ++k) acc[k] += cinert[10 * c + k];
+    }
+    for (int k = 0; k < 10; ++k) crb[10 * b + k] = acc[k];
+  }
+  gsync();
+  for (int i = lig; i < nv; i += G) {  // _M smooth.py:1048
+    int adr = ms.rowadr[i] + ms.rownnz[i] - 1;
+    float buf[6], ci[6];
+    for (int k = 0; k < 6; ++k) ci[k] = cdof[6 * i + k];
+    inert_vec(crb + 10 * dof_bodyid[i], ci, buf);
+    int j = i;
+    float arm = armature[i];
+    while (j >= 0) {
+      float s = 0.0f;
+      for (int k = 0; k < 6; ++k) s += cdof[6 * j + k] * buf[k];
+      M[adr] = s + arm;
+      arm = 0.0f;
+      --adr;
+      j = dof_parentid[j];
+    }
+  }
+  gsync();
+}
+
 // TAB: the model tables of every stage are staged in LDS (pos_tab_ok); otherwise the stages read the (per-world batched) model arrays
 template <int G, bool TAB>
 DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, float* smem, const Blk& b) {
@@ -489,55 +665,8 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
     const float* body_quat = bf(m.body_quat, m.body_quat_nb, w, 4 * nbody);
     const float* jnt_pos = bf(m.jnt_pos, m.jnt_pos_nb, w, 3 * njnt);
     const float* jnt_axis = bf(m.jnt_axis, m.jnt_axis_nb, w, 3 * njnt);
-    for (int l = 0; l < m.nbodylevel; ++l) {
-      const int beg = m.body_leveladr[l], end = m.body_leveladr[l + 1];
-      for (int idx = beg + lig; idx < end; idx += G) {
-        const int b = m.body_tree[idx];
-        if (b == 0) {
-          st3(xpos, V3{0, 0, 0});
-          st4(xquat, Q4{1, 0, 0, 0});
-          continue;
-        }
-        const int pid = m.body_parentid[b], jntadr = m.body_jntadr[b], jntnum = m.body_jntnum[b];
-        if (jntnum == 1 && m.jnt_type[jntadr] == JNT_FREE) {
-          const int qa = m.jnt_qposadr[jntadr];
-          V3 p = ld3(qpos + qa);
-          Q4 q = quat_normalize(ld4(qpos + qa + 3));
-          st3(xpos + 3 * b, p);
-          st4(xquat + 4 * b, q);
-          st3(xanchor + 3 * jntadr, p);
-          st3(xaxis + 3 * jntadr, ld3(jnt_axis + 3 * jntadr));
-          continue;
-        }
-        Q4 pq = ld4(xquat + 4 * pid);
-        // mocap bodies (children of the world without joints) take their pose from Data.mocap_* (smooth.py:104-108)
-        const int mid = m.nmocap ? m.body_mocapid[b] : -1;
-        const V3 bp = mid >= 0 ? ld3(d.mocap_pos + ((size_t)w * m.nmocap + mid) * 3) : ld3(body_pos + 3 * b);
-        const Q4 bq = mid >= 0 ? ld4(d.mocap_quat + ((size_t)w * m.nmocap + mid) * 4) : ld4(body_quat + 4 * b);
-        V3 pos = rot_vec_quat(bp, pq) + ld3(xpos + 3 * pid);
-        Q4 quat = mul_quat(pq, bq);
-        for (int j = jntadr; j < jntadr + jntnum; ++j) {
-          const int qa = m.jnt_qposadr[j], t = m.jnt_type[j];
-          V3 jp = ld3(jnt_pos + 3 * j), ja = ld3(jnt_axis + 3 * j);
-          V3 anchor = rot_vec_quat(jp, quat) + pos;
-          V3 axis = rot_vec_quat(ja, quat);
-          if (t == JNT_BALL) {
-            quat = mul_quat(quat, quat_normalize(ld4(qpos + qa)));
-            pos = anchor - rot_vec_quat(jp, quat);
-          } else if (t == JNT_SLIDE) {
-            pos = pos + axis * (qpos[qa] - qpos0[qa]);
-          } else if (t == JNT_HINGE) {
-            quat = mul_quat(quat, axis_angle_to_quat(ja, qpos[qa] - qpos0[qa]));
-            pos = anchor - rot_vec_quat(jp, quat);
-          }
-          st3(xanchor + 3 * j, anchor);
-          st3(xaxis + 3 * j, axis);
-        }
-        st3(xpos + 3 * b, pos);
-        st4(xquat + 4 * b, quat_normalize(quat));
-      }
-      gsync();
-    }
+    kin_levels<G>(m, true, d.mocap_pos + (size_t)w * m.nmocap * 3, d.mocap_quat + (size_t)w * m.nmocap * 4, qpos, qpos0, body_pos, body_quat, jnt_pos, jnt_axis, xpos, xquat,
+                  xanchor, xaxis, lig);
   }
   if (fk_fast) __syncthreads();  // (the level loop wrote poses into the slices of other wavefronts' worlds)
   if (!valid) return;
@@ -563,12 +692,7 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
   const int* dof_bodyid = TAB ? pt.dbody : m.dof_bodyid;
   const int* dof_parentid = TAB ? pt.dparent : m.dof_parentid;
   if (first <= POS_KINEMATICS) {
-    for (int b = lig; b < nbody; b += G) {
-      Q4 q = ld4(xquat + 4 * b);
-      quat_to_mat(q, xmat + 9 * b);
-      st3(xipos + 3 * b, ld3(xpos + 3 * b) + rot_vec_quat(ld3(body_ipos + 3 * b), q));
-      quat_to_mat(mul_quat(q, ld4(body_iquat + 4 * b)), ximat + 9 * b);
-    }
+    body_frames<G>(nbody, body_ipos, body_iquat, xpos, xquat, xmat, xipos, ximat, lig);
     pc.mark(6);
     {  // geoms and sites go straight to HBM (consumed by the collision kernel)
       for (int g = lig; g < m.ngeom; g += G) {
@@ -613,69 +737,8 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
       gcopy<G>(xaxis, d.xaxis + (size_t)w * 3 * njnt, 3 * njnt, lig);
       gsync();
     }
-    for (int b = lig; b < nbody; b += G) {  // subtree = contiguous id range (depth-first numbering)
-      V3 s = V3{0, 0, 0};
-      const int end = b + body_subtreenum[b];
-      for (int c = b; c < end; ++c) s = s + ld3(xipos + 3 * c) * body_mass[c];
-      const float mass = body_subtreemass[b];
-      if (mass != 0.0f) s = s * (1.0f / mass);
-      st3(scom + 3 * b, s);
-    }
-    gsync();
-    for (int b = lig; b < nbody; b += G) {  // _cinert smooth.py:733
-      const float* mat = ximat + 9 * b;
-      V3 in = ld3(body_inertia + 3 * b);
-      const float mass = body_mass[b];
-      V3 dif = ld3(xipos + 3 * b) - ld3(scom + 3 * body_rootid[b]);
-      float t00 = mat[0] * in.x * mat[0] + mat[1] * in.y * mat[1] + mat[2] * in.z * mat[2];
-      float t11 = mat[3] * in.x * mat[3] + mat[4] * in.y * mat[4] + mat[5] * in.z * mat[5];
-      float t22 = mat[6] * in.x * mat[6] + mat[7] * in.y * mat[7] + mat[8] * in.z * mat[8];
-      float t01 = mat[0] * in.x * mat[3] + mat[1] * in.y * mat[4] + mat[2] * in.z * mat[5];
-      float t02 = mat[0] * in.x * mat[6] + mat[1] * in.y * mat[7] + mat[2] * in.z * mat[8];
-      float t12 = mat[3] * in.x * mat[6] + mat[4] * in.y * mat[7] + mat[5] * in.z * mat[8];
-      float* r = cinert + 10 * b;
-      r[0] = t00 + mass * (dif.y * dif.y + dif.z * dif.z);
-      r[1] = t11 + mass * (dif.x * dif.x + dif.z * dif.z);
-      r[2] = t22 + mass * (dif.x * dif.x + dif.y * dif.y);
-      r[3] = t01 - mass * dif.x * dif.y;
-      r[4] = t02 - mass * dif.x * dif.z;
-      r[5] = t12 - mass * dif.y * dif.z;
-      r[6] = mass * dif.x;
-      r[7] = mass * dif.y;
-      r[8] = mass * dif.z;
-      r[9] = mass;
-    }
-    for (int j = lig; j < njnt; j += G) {  // _cdof smooth.py:779
-      const int b = jnt_bodyid[j], t = jnt_type[j];
-      int dof = jnt_dofadr[j];
-      const float* xm = xmat + 9 * b;
-      V3 off = ld3(scom + 3 * body_rootid[b]) - ld3(xanchor + 3 * j);
-      if (t == JNT_FREE || t == JNT_BALL) {
-        if (t == JNT_FREE) {
-          for (int k = 0; k < 3; ++k) {
-            float* c = cdof + 6 * (dof + k);
-            c[0] = c[1] = c[2] = 0.0f;
-            c[3] = k == 0 ? 1.0f : 0.0f;
-            c[4] = k == 1 ? 1.0f : 0.0f;
-            c[5] = k == 2 ? 1.0f : 0.0f;
-          }
-          dof += 3;
-        }
-        for (int k = 0; k < 3; ++k) {
-          V3 ax = V3{xm[k], xm[3 + k], xm[6 + k]};
-          st3(cdof + 6 * (dof + k), ax);
-          st3(cdof + 6 * (dof + k) + 3, cross(ax, off));
-        }
-      } else if (t == JNT_SLIDE) {
-        st3(cdof + 6 * dof, V3{0, 0, 0});
-        st3(cdof + 6 * dof + 3, ld3(xaxis + 3 * j));
-      } else {
-        V3 ax = ld3(xaxis + 3 * j);
-        st3(cdof + 6 * dof, ax);
-        st3(cdof + 6 * dof + 3, cross(ax, off));
-      }
-    }
-    gsync();
+    com_cinert_cdof<G>(nbody, njnt, body_mass, body_subtreemass, body_inertia, body_subtreenum, body_rootid, jnt_bodyid, jnt_dofadr, jnt_type, xmat, xipos, ximat, xanchor, xaxis,
+                       scom, cinert, cdof, lig);
     gcopy<G>(d.subtree_com + (size_t)w * 3 * nbody, scom, 3 * nbody, lig);
     gcopy<G>(d.cinert + (size_t)w * 10 * nbody, cinert, 10 * nbody, lig);
     gcopy<G>(d.cdof + (size_t)w * 6 * nv, cdof, 6 * nv, lig);
@@ -690,34 +753,7 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
       gcopy<G>(cdof, d.cdof + (size_t)w * 6 * nv, 6 * nv, lig);
       gsync();
     }
-    for (int b = lig; b < nbody; b += G) {
-      float acc[10];
-      for (int k = 0; k < 10; ++k) acc[k] = cinert[10 * b + k];
-      if (b > 0) {
-        const int end = b + body_subtreenum[b];
-        for (int c = b + 1; c < end; ++c)
-          for (int k = 0; k < 10; ++k) acc[k] += cinert[10 * c + k];
-      }
-      for (int k = 0; k < 10; ++k) crb[10 * b + k] = acc[k];
-    }
-    gsync();
-    for (int i = lig; i < nv; i += G) {  // _M smooth.py:1048
-      int adr = ms.rowadr[i] + ms.rownnz[i] - 1;
-      float buf[6], ci[6];
-      for (int k = 0; k < 6; ++k) ci[k] = cdof[6 * i + k];
-      inert_vec(crb + 10 * dof_bodyid[i], ci, buf);
-      int j = i;
-      float arm = armature[i];
-      while (j >= 0) {
-        float s = 0.0f;
-        for (int k = 0; k < 6; ++k) s += cdof[6 * j + k] * buf[k];
-        M[adr] = s + arm;
-        arm = 0.0f;
-        --adr;
-        j = dof_parentid[j];
-      }
-    }
-    gsync();
+    crb_mass_matrix<G>(ms, nbody, nv, armature, body_subtreenum, dof_bodyid, dof_parentid, cinert, cdof, crb, M, lig);
     gcopy<G>(d.crb + (size_t)w * 10 * nbody, crb, 10 * nbody, lig);
     gcopy<G>(d.M + (size_t)w * nC, M, nC, lig);
   }
