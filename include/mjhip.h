@@ -238,6 +238,12 @@ typedef struct MjhModel {
   const float* eq_solref; int eq_solref_nb;
   const float* eq_solimp; int eq_solimp_nb;
   const float* eq_data; int eq_data_nb;
+  /* contact sensors (csrc/sensor_contact.hpp; an addition within ABI v45: appended, so that every earlier field keeps its offset) */
+  int nsensor_contact;          /* sensors of type 42 (mjSENS_CONTACT); 0: the acceleration-stage sensor launch is not followed by k_sensor_contact */
+  int contact_sensor_maxmatch;  /* Option.contact_sensor_maxmatch: matches kept per (world, sensor), 1..64 (one wavefront: lane k owns match k)   */
+  const int* sensor_intprm;     /* [nsensor, 3] contact sensors: dataspec bits (found, force, torque, dist, pos, normal, tangent), reduce
+                                   (0 none, 1 mindist, 2 maxforce, 3 netforce), num slots; 0 for every other sensor                             */
+  const int* sensor_contact_adr; /* [nsensor] ids of the contact sensors first, -1 after them                                                   */
 } MjhModel;
 
 typedef struct MjhData {

@@ -261,7 +261,7 @@ def sensor_vel(m, d):
 
 def sensor_acc(m, d):
   """Acceleration-stage sensors only (reference sensor.sensor_acc, sensor.py:2512): accelerometer, force / torque / touch (after an
-  rne_postconstraint launch when one of them is present), frame accelerations, actuator forces; call after the solver."""
+  rne_postconstraint launch when one of them is present), frame accelerations, actuator forces, contact sensors; call after the solver."""
   _run(_S["MJH_STAGE_SENSOR_ACC"], m, d)
 
 

@@ -346,6 +346,7 @@ def _options(mjm, m):
   o.graph_conditional = False
   o.run_collision_detection = True
   o.warn_overflow = False
+  o.contact_sensor_maxmatch = _check_maxmatch(_numeric(mjm, "contact_sensor_maxmatch", CONTACT_SENSOR_MAXMATCH_CAP))
   return o, s, dict(
     opt_timestep=np.array([opt.timestep], dtype=f32),
     # float32 device arithmetic cannot resolve MuJoCo's default 1e-8 (io.py:398-401)
@@ -450,6 +451,7 @@ _OPTIONAL_FIELDS = {
     """mat_rgba mesh_vertadr mesh_vertnum mesh_vert mesh_face mesh_faceadr mesh_graph mesh_polyadr mesh_polynormal mesh_polyvertadr
     mesh_polyvertnum mesh_polyvert mesh_polymapadr mesh_polymapnum mesh_polymap hfield_size hfield_nrow hfield_ncol hfield_adr hfield_data
     sensor_type sensor_datatype sensor_objtype sensor_objid sensor_reftype sensor_refid sensor_dim sensor_adr sensor_cutoff
+    sensor_intprm sensor_contact_adr
     pair_dim pair_friction pair_solref pair_solreffriction pair_solimp pair_margin pair_gap site_bodyid site_pos site_quat
     eq_obj1id eq_obj2id eq_solref eq_solimp eq_data""".split()),
 }
@@ -483,7 +485,55 @@ def _sensor_facts(sensor_type):
 
     warnings.warn(f"sensor types {sorted(set(bad))} are not computed by this engine (csrc/sensor.hpp computes {sorted(supported)}): their sensordata entries are 0")
   count = lambda kinds: int(sum(int(t) in kinds for t in sensor_type))
-  return dict(nsensor_acc=count((0, 1, 4, 5, 22, 33, 34)), nsensor_energy=count((43, 44)), nsensor_frc=count((4, 5)), nsensor_subtree=count((36, 37)))
+  return dict(nsensor_acc=count((0, 1, 4, 5, 22, 33, 34, 42)), nsensor_energy=count((43, 44)), nsensor_frc=count((4, 5)), nsensor_subtree=count((36, 37)),
+              nsensor_contact=count((42,)))
+
+
+CONTACT_SENSOR_MAXMATCH_CAP = 64  # csrc/sensor_contact.hpp: one wavefront per world, lane k owns match k
+
+
+def _check_maxmatch(value):
+  value = int(value)
+  if value < 1 or value > CONTACT_SENSOR_MAXMATCH_CAP:
+    raise ValueError(f"contact_sensor_maxmatch = {value}: must be in 1..{CONTACT_SENSOR_MAXMATCH_CAP} (the contact-sensor kernel keeps the matches of a world's "
+                     f"sensor in the {CONTACT_SENSOR_MAXMATCH_CAP} lanes of one wavefront)")
+  return value
+
+
+def _numeric(mjm, name, default):
+  """First value of the custom numeric `name` of the host model (reference io.py:409-413), `default` when the model has none: the numpy
+  stand-in lists its numerics' names; a mujoco.MjModel answers by name."""
+  names = getattr(mjm, "numeric_names", None)
+  if names is not None:
+    return float(np.asarray(mjm.numeric_data)[int(np.asarray(mjm.numeric_adr)[list(names).index(name)])]) if name in names else default
+  try:
+    return float(mjm.numeric(name).data[0])
+  except (AttributeError, KeyError, TypeError):
+    return default
+
+
+def _contact_sensor_tables(host, nsensor_contact):
+  """sensor_intprm [nsensor, 3] and sensor_contact_adr [nsensor] of the model whose other sensor tables are in `host`; checks what
+  csrc/sensor_contact.hpp relies on."""
+  from .mjcf import contact_slot_size
+
+  stype, n = host["sensor_type"], len(host["sensor_type"])
+  intprm = host["sensor_intprm"]
+  if intprm.shape[0] != n:
+    if nsensor_contact:
+      raise ValueError(f"sensor_intprm has {intprm.shape[0]} rows for {n} sensors, and the model has contact sensors")
+    intprm = np.zeros((n, 3), dtype=np.int32)
+  ids = np.flatnonzero(stype == 42).astype(np.int32)
+  count = {0: 0, 1: len(host["body_parentid"]), 2: len(host["body_parentid"]), 5: len(host["geom_bodyid"]), 6: len(host["site_type"])}  # per mjtObj
+  for i in ids:
+    for which, types_ok in (("obj", (0, 1, 2, 5, 6)), ("ref", (0, 1, 2, 5))):  # (the kernel indexes the body / geom / site tables with these)
+      t, k = int(host[f"sensor_{which}type"][i]), int(host[f"sensor_{which}id"][i])
+      if t not in types_ok or (t != 0 and not 0 <= k < count[t]):
+        raise ValueError(f"contact sensor {i}: sensor_{which}type {t} / sensor_{which}id {k} is not an object of the model a contact sensor can name")
+    spec, reduce, num = (int(x) for x in intprm[i])
+    if not (0 < spec < 128 and 0 <= reduce <= 3 and num >= 1 and int(host["sensor_dim"][i]) == num * contact_slot_size(spec)):
+      raise ValueError(f"contact sensor {i}: sensor_intprm {intprm[i].tolist()} (dataspec, reduce, num) does not agree with sensor_dim {int(host['sensor_dim'][i])}")
+  return dict(sensor_intprm=np.ascontiguousarray(intprm, dtype=np.int32), sensor_contact_adr=np.concatenate([ids, np.full(n - len(ids), -1, dtype=np.int32)]))
 
 
 def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
@@ -518,6 +568,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     setattr(m, size, int(host[name].shape[0]))
   for name, value in {**_sensor_facts(host["sensor_type"]), **_ray_facts(host)}.items():
     setattr(m, name, value)
+  host.update(_contact_sensor_tables(host, m.nsensor_contact))
   m.sleep_enabled = int(bool(int(opt.enableflags) & int(types.EnableBit.SLEEP)) and not (int(opt.disableflags) & int(types.DisableBit.ISLAND)))
   m.opt_sleep_tolerance = float(getattr(opt, "sleep_tolerance", 1e-4))
   if m.sleep_enabled and (host["tree_sleep_policy"] > int(types.SleepPolicy.AUTO_ALLOWED)).any():
@@ -610,6 +661,7 @@ _C_MODEL_SCALARS = {
   **{name: (lambda m, name=name: int(getattr(m.opt, name)))
      for name in ("integrator", "cone", "solver", "iterations", "ls_iterations", "enableflags", "broadphase", "broadphase_filter", "ccd_iterations")},
   "disableflags": _c_disableflags, "opt_sleep_tolerance": lambda m: float(m.opt_sleep_tolerance), "heavy_colliders": _c_heavy_colliders,
+  "contact_sensor_maxmatch": lambda m: _check_maxmatch(m.opt.contact_sensor_maxmatch),
 }
 
 

@@ -1559,6 +1559,15 @@ def _compile(root, base_dir):
   m.camera = MjCamera(cameras)
   m.nuserdata = 0
   _compile_sensors(m, root, [s_["name"] for s_ in sites])
+  # <custom><numeric>: kept as MuJoCo lays them out (numeric_adr / numeric_size / numeric_data) plus their names; the engine reads one of
+  # them, contact_sensor_maxmatch (io.put_model), the rest of <custom> stays ignored
+  numerics = [(e.get("name", ""), _floats(e.get("data", "0")), int(e.get("size", 0))) for sec in root.findall("custom") for e in sec.findall("numeric")]
+  numerics = [(name, data + [0.0] * (size - len(data))) for name, data, size in numerics]
+  m.nnumeric = len(numerics)
+  m.numeric_names = [name for name, _ in numerics]
+  m.numeric_size = np.array([len(data) for _, data in numerics], dtype=np.int32)
+  m.numeric_adr = np.concatenate([[0], np.cumsum(m.numeric_size)[:-1]]).astype(np.int32) if numerics else np.zeros(0, dtype=np.int32)
+  m.numeric_data = np.array([x for _, data in numerics for x in data], dtype=np.float64)
 
   _sparse_structure(m)
   set_const(m)
@@ -1571,17 +1580,56 @@ def _compile(root, base_dir):
 # mjtSensor / mjtObj / mjtDataType / mjtStage values used below (MuJoCo's enums; UNPINNED here -- the mujoco package is absent: a real
 # MjModel carries its own numbers in sensor_type, which put_model compares with these)
 SENS = {"touch": 0, "accelerometer": 1, "force": 4, "torque": 5, "magnetometer": 6, "jointactuatorfrc": 16, "jointlimitpos": 20, "jointlimitvel": 21, "jointlimitfrc": 22, "e_potential": 43, "e_kinetic": 44, "framelinacc": 33, "frameangacc": 34, "velocimeter": 2, "gyro": 3, "jointpos": 9, "jointvel": 10, "actuatorpos": 13, "actuatorvel": 14, "actuatorfrc": 15, "ballquat": 18, "ballangvel": 19,
-        "framepos": 26, "framequat": 27, "framexaxis": 28, "frameyaxis": 29, "framezaxis": 30, "framelinvel": 31, "frameangvel": 32, "subtreecom": 35, "subtreelinvel": 36, "subtreeangmom": 37, "clock": 45, "rangefinder": 7}
+        "framepos": 26, "framequat": 27, "framexaxis": 28, "frameyaxis": 29, "framezaxis": 30, "framelinvel": 31, "frameangvel": 32, "subtreecom": 35, "subtreelinvel": 36, "subtreeangmom": 37, "clock": 45, "rangefinder": 7, "contact": 42}
 # sensors that keep their slot in sensordata (the reference's layout) but are not computed: the engine writes zeros and put_model warns
 SENS_UNSUPPORTED = {}
 _SENS_DIM = {"touch": 1, "rangefinder": 1, "ballquat": 4, "framequat": 4, "jointactuatorfrc": 1, "jointlimitpos": 1, "jointlimitvel": 1, "jointlimitfrc": 1, "e_potential": 1, "e_kinetic": 1, "jointpos": 1, "jointvel": 1, "actuatorpos": 1, "actuatorvel": 1, "actuatorfrc": 1, "clock": 1}
-_SENS_STAGE = {"velocimeter": 2, "gyro": 2, "jointvel": 2, "actuatorvel": 2, "ballangvel": 2, "framelinvel": 2, "frameangvel": 2, "subtreelinvel": 2, "subtreeangmom": 2, "jointlimitvel": 2, "e_kinetic": 2, "touch": 3, "jointlimitfrc": 3, "jointactuatorfrc": 3, "actuatorfrc": 3, "accelerometer": 3, "force": 3, "torque": 3, "framelinacc": 3, "frameangacc": 3}  # default: POS (1)
+_SENS_STAGE = {"velocimeter": 2, "gyro": 2, "jointvel": 2, "actuatorvel": 2, "ballangvel": 2, "framelinvel": 2, "frameangvel": 2, "subtreelinvel": 2, "subtreeangmom": 2, "jointlimitvel": 2, "e_kinetic": 2, "touch": 3, "jointlimitfrc": 3, "jointactuatorfrc": 3, "actuatorfrc": 3, "accelerometer": 3, "force": 3, "torque": 3, "framelinacc": 3, "frameangacc": 3, "contact": 3}  # default: POS (1)
 _OBJ = {"body": 1, "xbody": 2, "geom": 5, "site": 6, "camera": 7}
+# <contact> sensor (mjSENS_CONTACT): the data fields in their canonical order with the floats each takes in a slot -- bit i of
+# sensor_intprm[:, 0] stands for field i --, and the reductions of sensor_intprm[:, 1] (reference sensor.py:1810-1851)
+CONTACT_DATA = (("found", 1), ("force", 3), ("torque", 3), ("dist", 1), ("pos", 3), ("normal", 3), ("tangent", 3))
+CONTACT_REDUCE = {"none": 0, "mindist": 1, "maxforce": 2, "netforce": 3}
+
+
+def contact_slot_size(dataspec):
+  """Floats of one slot of a contact sensor with these dataspec bits."""
+  return sum(n for i, (_, n) in enumerate(CONTACT_DATA) if dataspec >> i & 1)
+
+
+def _contact_sensor(a, lookup):
+  """(objtype, objid, reftype, refid, intprm, dim) of a <contact> sensor element's attributes."""
+  def pick(attrs, what):
+    given = [k for k in attrs if k in a]
+    if len(given) > 1:
+      raise ValueError(f"contact sensor {a.get('name', '')!r}: at most one of {' / '.join(attrs)} ({what} object), got {given}")
+    if not given:
+      return 0, -1  # mjOBJ_UNKNOWN: any
+    objtype = {"geom": 5, "body": 1, "subtree": 2, "site": 6}[given[0].rstrip("12")]
+    if a[given[0]] not in lookup[objtype]:
+      raise ValueError(f"contact sensor {a.get('name', '')!r}: unknown {given[0]} {a[given[0]]!r}")
+    return objtype, lookup[objtype].index(a[given[0]])
+  objtype, objid = pick(("geom1", "body1", "subtree1", "site"), "first")
+  reftype, refid = pick(("geom2", "body2", "subtree2"), "second")
+  names = [n for n, _ in CONTACT_DATA]
+  words = a.get("data", "found").split()
+  order = [names.index(x) if x in names else -1 for x in words]
+  if not words or -1 in order:
+    raise ValueError(f"contact sensor {a.get('name', '')!r}: data must name fields of {names}, got {a.get('data')!r}")
+  if any(j <= i for i, j in zip(order, order[1:])):
+    raise ValueError(f"contact sensor {a.get('name', '')!r}: data fields must come in the order {' '.join(names)} without repeats, got {a.get('data')!r}")
+  if a.get("reduce", "none") not in CONTACT_REDUCE:
+    raise ValueError(f"contact sensor {a.get('name', '')!r}: reduce must be one of {sorted(CONTACT_REDUCE)}, got {a.get('reduce')!r}")
+  num = int(a.get("num", 1))
+  if num < 1:
+    raise ValueError(f"contact sensor {a.get('name', '')!r}: num must be at least 1")
+  dataspec = sum(1 << i for i in order)
+  return objtype, objid, reftype, refid, (dataspec, CONTACT_REDUCE[a.get("reduce", "none")], num), num * contact_slot_size(dataspec)
 
 
 def _compile_sensors(m, root, site_names):
-  """<sensor> section, the subset csrc/sensor.hpp computes (reference sensor.py: joint / actuator / ball / frame / IMU-style site sensors,
-  subtree centre of mass, clock); anything else raises."""
+  """<sensor> section, the subset csrc/sensor.hpp and csrc/sensor_contact.hpp compute (reference sensor.py: joint / actuator / ball / frame /
+  IMU-style site sensors, subtree centre of mass, clock, contact); anything else raises."""
   rows = []
   lookup = {1: m.body_names, 2: m.body_names, 5: m.geom_names, 6: site_names}
   for sec in root.findall("sensor"):
@@ -1593,8 +1641,10 @@ def _compile_sensors(m, root, site_names):
         continue
       if e.tag not in SENS:
         raise NotImplementedError(f"sensor <{e.tag}> is not implemented")
-      objtype, objid, reftype, refid = 0, -1, 0, -1
-      if e.tag in ("jointactuatorfrc", "jointlimitpos", "jointlimitvel", "jointlimitfrc"):
+      objtype, objid, reftype, refid, intprm, dim = 0, -1, 0, -1, (0, 0, 0), _SENS_DIM.get(e.tag, 3)
+      if e.tag == "contact":
+        objtype, objid, reftype, refid, intprm, dim = _contact_sensor(a, lookup)
+      elif e.tag in ("jointactuatorfrc", "jointlimitpos", "jointlimitvel", "jointlimitfrc"):
         objtype, objid = 3, m.jnt_names.index(a["joint"])
       elif e.tag in ("jointpos", "jointvel", "ballquat", "ballangvel"):
         objtype, objid = 3, m.jnt_names.index(a["joint"])  # mjOBJ_JOINT
@@ -1613,11 +1663,11 @@ def _compile_sensors(m, root, site_names):
         if "reftype" in a:
           reftype = _OBJ[a["reftype"]]
           refid = lookup[reftype].index(a["refname"])
-      dim = _SENS_DIM.get(e.tag, 3)
       rows.append(dict(type=SENS[e.tag], datatype=1 if e.tag == "touch" else 3 if e.tag in ("ballquat", "framequat") else (2 if e.tag.startswith("frame") and e.tag.endswith("axis") else 0),
                        needstage=_SENS_STAGE.get(e.tag, 1), objtype=objtype, objid=objid, reftype=reftype, refid=refid, dim=dim,
-                       cutoff=float(a.get("cutoff", 0.0)), name=a.get("name", "")))
+                       cutoff=float(a.get("cutoff", 0.0)), name=a.get("name", ""), intprm=intprm))
   m.nsensor = len(rows)
+  m.sensor_intprm = np.array([r.get("intprm", (0, 0, 0)) for r in rows], dtype=np.int32).reshape(len(rows), 3)
   for k in ("type", "datatype", "needstage", "objtype", "objid", "reftype", "refid", "dim"):
     setattr(m, "sensor_" + k, np.array([r[k] for r in rows], dtype=np.int32))
   m.sensor_cutoff = np.array([r["cutoff"] for r in rows], dtype=np.float64)

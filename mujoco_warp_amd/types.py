@@ -293,6 +293,7 @@ class Option(_Dirty):
   graph_conditional: bool = False
   run_collision_detection: bool = False
   warn_overflow: bool = False
+  contact_sensor_maxmatch: int = 64  # matches kept per (world, contact sensor): 1..64, one wavefront (reference types.py Option.contact_sensor_maxmatch)
 
 @dataclasses.dataclass(eq=False)
 class Statistic(_Dirty):
@@ -492,6 +493,10 @@ class Model(_Dirty):
   sensor_dim: DeviceArray = _arr(('nsensor',), "int32")
   sensor_adr: DeviceArray = _arr(('nsensor',), "int32")
   sensor_cutoff: DeviceArray = _arr(('nsensor',), "float32")
+  # contact sensors (csrc/sensor_contact.hpp; reference types.py Model.sensor_intprm / sensor_contact_adr)
+  nsensor_contact: int = 0
+  sensor_intprm: DeviceArray = _arr(('nsensor', 3), "int32")  # contact sensors: dataspec bits, reduce, num; 0 elsewhere
+  sensor_contact_adr: DeviceArray = _arr(('nsensor',), "int32")  # ids of the contact sensors first, -1 after them
   nmeshgraph: int = 0
   nhfielddata: int = 0
   hfield_size: DeviceArray = _arr(('nhfield', 4), "float32")
