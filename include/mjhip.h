@@ -174,6 +174,10 @@ typedef struct MjhModel {
   const int* sensor_type; const int* sensor_datatype; const int* sensor_objtype; const int* sensor_objid; const int* sensor_reftype; const int* sensor_refid;
   const int* sensor_dim; const int* sensor_adr;
   const float* sensor_cutoff;
+  /* geom distance sensors (csrc/sensor_collision.hpp; an addition within ABI v45 that is NOT at the tail: the offsets of every later field move) */
+  int nsensor_collision;            /* sensors of types 39..41 (mjSENS_GEOMDIST / GEOMNORMAL / GEOMFROMTO); 0: k_sensor_collision is not launched */
+  const int* sensor_collision_adr;  /* [nsensor] ids of those sensors first, -1 after them */
+  const int* body_geomnum; const int* body_geomadr; /* [nbody] the geoms of a body: a sensor side that names a body ranges over them */
   /* height fields (types.py: hfield_*; geom_dataid of an hfield geom is its height field) */
   int nhfield;
   const float* hfield_size;     /* [nhfield, 4] x, y half sizes, top scale of the elevation data, base thickness */

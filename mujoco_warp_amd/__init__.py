@@ -106,6 +106,7 @@ from .types import Model
 from .types import ObjType
 from .types import Option
 from .types import OverflowType
+from .types import SensorType
 from .types import SleepPolicy
 from .types import SleepState
 from .types import SolverType

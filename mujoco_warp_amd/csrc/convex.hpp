@@ -467,7 +467,7 @@ DEV V3 ccd_combine(int n, const float (&lam)[4], const V3 (&m)[4]) {
   return o;
 }
 
-template <int CG = 0>
+template <int CG = 0, bool GUARD = false>
 DEV void ccd_gjk(float tolerance, int iterations, const CcdGeom& g1, const CcdGeom& g2, V3 x1_0, V3 x2_0, float cutoff, bool is_discrete,
                  GjkOut& res, int lig = 0) {
   int n = 0;
@@ -476,6 +476,12 @@ DEV void ccd_gjk(float tolerance, int iterations, const CcdGeom& g1, const CcdGe
   const float epsilon = is_discrete ? 0.0f : 0.5f * tolerance * tolerance, min_norm = is_discrete ? CCD_MINVAL : tolerance;
   V3 xk = x1_0 - x2_0;
   float xnorm = sqrtf(dot(xk, xk)), xnorm_prev = 0.0f;
+  // GUARD (the distance sensors, csrc/sensor_collision.hpp; dead code in every other instantiation): the largest proven lower bound of the
+  // distance, and the smallest sound |x_k| with its witness points
+  float guard_lb = 0.0f, bnorm = CCD_FLOAT_MAX;
+  V3 bx1 = x1_0, bx2 = x2_0, bxk = xk;
+  int bn = 0;
+  bool refused = false;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     res.s[i] = res.s1[i] = res.s2[i] = V3{0.0f, 0.0f, 0.0f};
@@ -555,6 +561,27 @@ DEV void ccd_gjk(float tolerance, int iterations, const CcdGeom& g1, const CcdGe
     }
     n = mcount;
     if (n < 1) break;
+    if constexpr (GUARD) {
+      // The closest points of successive simplices approach the distance from above and never fall below a proven lower bound
+      // x_j . s_j / |x_j| of it.  In float32 neither holds once the support points lie close together on a curved rim, nearly collinear:
+      // the sub-distance solve loses its digits, its "closest point" lands outside the Minkowski difference (then the duality gap turns
+      // negative and the loop ends on it), or two simplices alternate until the iterations run out.  A closest point below the bound
+      // is refused and ends the loop; the smallest sound |x_k| and its witness points are what the function returns.
+      guard_lb = fmaxf(guard_lb, lower / xnorm);
+      const V3 xn = ccd_combine(n, lam, res.s);
+      const float nn = sqrtf(dot(xn, xn));
+      if (guard_lb > 0.0f && nn < guard_lb - 4e-7f * nn) {
+        refused = true;
+        break;
+      }
+      if (nn < bnorm) {
+        bnorm = nn;
+        bxk = xn;
+        bx1 = ccd_combine(n, lam, res.s1);
+        bx2 = ccd_combine(n, lam, res.s2);
+        bn = n;
+      }
+    }
     xk = ccd_combine(n, lam, res.s);
     xnorm_prev = xnorm;
     xnorm = sqrtf(dot(xk, xk));
@@ -564,6 +591,16 @@ DEV void ccd_gjk(float tolerance, int iterations, const CcdGeom& g1, const CcdGe
   res.separated = false;
   res.x1 = n == 0 ? x1_0 : ccd_combine(n, lam, res.s1);
   res.x2 = n == 0 ? x2_0 : ccd_combine(n, lam, res.s2);
+  if constexpr (GUARD) {
+    // (the last simplex is the best one unless it was refused or the iterates went up again; a pair that touches keeps its simplex for EPA)
+    if (n < 4 && bnorm < CCD_FLOAT_MAX && bnorm > tolerance && (refused || bnorm < xnorm)) {
+      xk = bxk;
+      xnorm = bnorm;
+      res.x1 = bx1;
+      res.x2 = bx2;
+      n = bn;
+    }
+  }
   if (xnorm > 0.0f) {
     const V3 dir = xk * (1.0f / xnorm);
     int v;
@@ -956,7 +993,7 @@ DEV bool ccd_is_discrete(const CcdGeom& g1, const CcdGeom& g2) {
 // gjk_phase (collision_gjk.py:2350-2418).  Returns 1: done -- dist_out / x1 / x2 are the result (CCD_FLOAT_MAX: separated) --, 2: the
 // pair penetrates and EPA must run from the simplex in `res`; g1 / g2 leave with their margins and sizes restored and the mesh vertex
 // caches (`index`) of the last support calls: the state epa_phase continues from.
-template <int CG = 0>
+template <int CG = 0, bool GUARD = false>
 DEV int ccd_gjk_phase(float tolerance, float cutoff, int gjk_iterations, CcdGeom& g1, CcdGeom& g2, float& dist_out, V3& x1, V3& x2, GjkOut& res, int lig = 0) {
   const CcdGeom o1 = g1, o2 = g2;
   float full1 = 0.0f, full2 = 0.0f, size1 = 0.0f, size2 = 0.0f;
@@ -975,7 +1012,7 @@ DEV int ccd_gjk_phase(float tolerance, float cutoff, int gjk_iterations, CcdGeom
   }
   if (size1 + size2 > 0.0f) {
     cutoff += full1 + full2;
-    ccd_gjk<CG>(tolerance, gjk_iterations, g1, g2, g1.pos, g2.pos, cutoff, is_discrete, res, lig);
+    ccd_gjk<CG, GUARD>(tolerance, gjk_iterations, g1, g2, g1.pos, g2.pos, cutoff, is_discrete, res, lig);
     if (res.dist > tolerance) {
       dist_out = res.dist;
       x1 = res.x1;
@@ -993,7 +1030,7 @@ DEV int ccd_gjk_phase(float tolerance, float cutoff, int gjk_iterations, CcdGeom
     g2.size = o2.size;
     cutoff -= full1 + full2;
   }
-  ccd_gjk<CG>(tolerance, gjk_iterations, g1, g2, g1.pos, g2.pos, cutoff, is_discrete, res, lig);
+  ccd_gjk<CG, GUARD>(tolerance, gjk_iterations, g1, g2, g1.pos, g2.pos, cutoff, is_discrete, res, lig);
   dist_out = res.dist;
   x1 = res.x1;
   x2 = res.x2;

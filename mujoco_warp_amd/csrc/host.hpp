@@ -10,6 +10,7 @@
 //   pgs_tu.hip (k_solve_pgs, k_solve_pgs_big), solve_big.hip (k_solve_big), render_tu.hip (k_render, k_camera_rays: the cameras),
 //   set_const_tu.hip (k_set_const and its entry point mjh_set_const: the derived model constants),
 //   sensor_contact_tu.hip (k_sensor_contact: the contact sensors behind the acceleration-stage sensor launch),
+//   sensor_collision_tu.hip (k_sensor_collision: the geom distance sensors behind the position-stage sensor launch),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
@@ -168,3 +169,5 @@ int launch_render(const MjhModel* m, const MjhData* d, const MjhRender* rc, hipS
 int launch_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc, float* pnt, float* vec, hipStream_t s);
 // contact sensors (sensor_contact.hpp, sensor_contact_tu.hip): one wavefront per world, after k_sensor of the acceleration stage
 int launch_sensor_contact(const MjhModel* m, const MjhData* d, hipStream_t s);
+// geom distance sensors (sensor_collision.hpp, sensor_collision_tu.hip): one wavefront per (world, sensor), after k_sensor of the position stage
+int launch_sensor_collision(const MjhModel* m, const MjhData* d, hipStream_t s);

@@ -255,8 +255,9 @@ static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStre
     TRY(launch_subtree_vel(m, d, s));
   }
   if (!d->sensordata) return fail(MJH_E_ARG, "Data.sensordata missing (allocate Data with make_data/put_data)");
-  if (m->nsensor > m->nsensor_contact)  // (a model whose sensors are all contact sensors has nothing for k_sensor)
+  if (m->nsensor > m->nsensor_contact + m->nsensor_collision)  // (a model whose sensors are all contact / geom distance sensors has nothing for k_sensor)
     hipLaunchKernelGGL(k_sensor, dim3((d->nworld * m->nsensor + 255) / 256), dim3(256), 0, s, *m, *d, stage);
+  if (stage == 0 && m->nsensor_collision > 0) TRY(launch_sensor_collision(m, d, s));  // (k_sensor skips their slots)
   if (stage == 1 && m->nsensor_contact > 0) TRY(launch_sensor_contact(m, d, s));  // (k_sensor skips their slots)
   return MJH_OK;
 }

@@ -5,14 +5,16 @@
 // already integrate the state: Data.qpos / qvel / time must still be the step's inputs when JOINTPOS / JOINTVEL / CLOCK are read).
 // Acceleration-stage sensors (accelerometer, force, torque, touch, frame accelerations, joint limit force) are written by a second launch
 // after the solver.  Contact sensors (type 42) have a kernel of their own behind that launch: csrc/sensor_contact.hpp; k_sensor skips them.
-// Not built: tendon and camera sensors, geomdist / insidesite / tactile (the loader raises).
+// Geom distance sensors (types 39..41) likewise, behind the position-stage launch: csrc/sensor_collision.hpp.
+// Not built: tendon and camera sensors, tactile (the loader raises).
 #pragma once
 #include "dev_common.hpp"
 #include "ray.hpp"
+#include "site_inside.hpp"
 
 enum { SENS_TOUCH = 0, SENS_ACCELEROMETER = 1, SENS_FORCE = 4, SENS_TORQUE = 5, SENS_MAGNETOMETER = 6, SENS_VELOCIMETER = 2, SENS_GYRO = 3, SENS_JOINTPOS = 9, SENS_JOINTVEL = 10, SENS_ACTUATORPOS = 13, SENS_ACTUATORVEL = 14, SENS_ACTUATORFRC = 15,
        SENS_JOINTACTFRC = 16, SENS_BALLQUAT = 18, SENS_BALLANGVEL = 19, SENS_JOINTLIMITPOS = 20, SENS_JOINTLIMITVEL = 21, SENS_JOINTLIMITFRC = 22, SENS_FRAMEPOS = 26, SENS_FRAMEQUAT = 27, SENS_FRAMEXAXIS = 28, SENS_FRAMEYAXIS = 29, SENS_FRAMEZAXIS = 30,
-       SENS_FRAMELINVEL = 31, SENS_FRAMEANGVEL = 32, SENS_FRAMELINACC = 33, SENS_FRAMEANGACC = 34, SENS_SUBTREECOM = 35, SENS_SUBTREELINVEL = 36, SENS_SUBTREEANGMOM = 37, SENS_CONTACT = 42, SENS_E_POTENTIAL = 43, SENS_E_KINETIC = 44, SENS_CLOCK = 45, SENS_RANGEFINDER = 7 };
+       SENS_FRAMELINVEL = 31, SENS_FRAMEANGVEL = 32, SENS_FRAMELINACC = 33, SENS_FRAMEANGACC = 34, SENS_SUBTREECOM = 35, SENS_SUBTREELINVEL = 36, SENS_SUBTREEANGMOM = 37, SENS_INSIDESITE = 38, SENS_GEOMDIST = 39, SENS_GEOMNORMAL = 40, SENS_GEOMFROMTO = 41, SENS_CONTACT = 42, SENS_E_POTENTIAL = 43, SENS_E_KINETIC = 44, SENS_CLOCK = 45, SENS_RANGEFINDER = 7 };
 enum { OBJ_BODY = 1, OBJ_XBODY = 2, OBJ_GEOM = 5, OBJ_SITE = 6 };
 
 struct SensFrame {
@@ -137,7 +139,8 @@ __global__ void __launch_bounds__(256) k_sensor(MjhModel m, MjhData d, int stage
   const int w = idx / ns, i = idx - w * ns;
   const int t = m.sensor_type[i], id = m.sensor_objid[i], ot = m.sensor_objtype[i], rid = m.sensor_refid[i], rt = m.sensor_reftype[i];
   const bool acc_type = t == SENS_ACCELEROMETER || t == SENS_FRAMELINACC || t == SENS_FRAMEANGACC || t == SENS_FORCE || t == SENS_TORQUE || t == SENS_JOINTLIMITFRC || t == SENS_TOUCH;
-  if (t == SENS_CONTACT || acc_type != (stage == 1)) return;  // (contact sensors: k_sensor_contact, csrc/sensor_contact.hpp)
+  // (contact sensors: k_sensor_contact, csrc/sensor_contact.hpp; geom distance sensors: k_sensor_collision, csrc/sensor_collision.hpp)
+  if (t == SENS_CONTACT || (t >= SENS_GEOMDIST && t <= SENS_GEOMFROMTO) || acc_type != (stage == 1)) return;
   float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   auto put3 = [&](V3 a) {
     v[0] = a.x;
@@ -174,6 +177,8 @@ __global__ void __launch_bounds__(256) k_sensor(MjhModel m, MjhData d, int stage
     // (models with mesh triangles / height fields: the serial walk over those too -- the same choice mjh_rays makes)
     v[0] = (m.nmeshface > 0 || m.nhfield > 0) ? ray_world_full(m, d, w, p, z, all, 1, m.site_bodyid[id], g, n) : ray_world(m, d, w, p, z, all, 1, m.site_bodyid[id], g, n);
   }
+  else if (t == SENS_INSIDESITE)  // sensor.py:719-746: the object's position (body: xipos, xbody: xpos, geom, site) against the volume of site `rid`
+    v[0] = cs_inside(m.site_type[rid], ld3(m.site_size + 3 * rid), ld3(d.site_xpos + ((size_t)w * m.nsite + rid) * 3), d.site_xmat + ((size_t)w * m.nsite + rid) * 9, sens_frame(m, d, w, ot, id).pos) ? 1.0f : 0.0f;
   else if (t == SENS_SUBTREECOM) put3(ld3(d.subtree_com + ((size_t)w * m.nbody + id) * 3));
   else if (t == SENS_SUBTREELINVEL) put3(ld3(d.subtree_linvel + ((size_t)w * m.nbody + id) * 3));  // (k_subtree_vel ran just before)
   else if (t == SENS_SUBTREEANGMOM) put3(ld3(d.subtree_angmom + ((size_t)w * m.nbody + id) * 3));

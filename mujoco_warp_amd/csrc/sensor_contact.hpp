@@ -20,6 +20,7 @@
 // Not built: contact_sensor_maxmatch > 64, sensor noise, cutoff (the reference applies none to contact sensors).
 #pragma once
 #include "dev_common.hpp"
+#include "site_inside.hpp"
 
 #define OVF_CONTACT_MATCH (1 << 6) /* OverflowType.CONTACT_MATCH (types.py) */
 #define CS_FSTRIDE 7
@@ -34,25 +35,6 @@ __host__ __device__ static inline int cs_lds_words(int concap) { return (CS_FSTR
 DEV int cs_slot_size(int spec) {
   return ((spec & CS_FOUND) ? 1 : 0) + ((spec & CS_FORCE) ? 3 : 0) + ((spec & CS_TORQUE) ? 3 : 0) + ((spec & CS_DIST) ? 1 : 0) + ((spec & CS_POS) ? 3 : 0) + ((spec & CS_NORMAL) ? 3 : 0) +
          ((spec & CS_TANGENT) ? 3 : 0);
-}
-
-// util_misc.py:676-705 inside_geom: is the point strictly inside the site's volume
-DEV bool cs_inside(int type, V3 size, V3 pos, const float* mat, V3 point) {
-  const V3 vec = point - pos;
-  if (type == G_SPHERE) return dot(vec, vec) < size.x * size.x;
-  const V3 p = matT_mul(mat, vec);
-  if (type == G_CAPSULE) {
-    const float zd = p.z - fminf(fmaxf(p.z, -size.y), size.y);
-    return p.x * p.x + p.y * p.y + zd * zd < size.x * size.x;
-  }
-  if (type == G_ELLIPSOID) {
-    const V3 q = V3{p.x / size.x, p.y / size.y, p.z / size.z};
-    return dot(q, q) < 1.0f;
-  }
-  if (type == G_CYLINDER) return fabsf(p.z) < size.y && p.x * p.x + p.y * p.y < size.x * size.x;
-  if (type == G_BOX) return fabsf(p.x) < size.x && fabsf(p.y) < size.y && fabsf(p.z) < size.z;
-  if (type == G_PLANE) return p.z < 0.0f;
-  return false;
 }
 
 // sensor.py:2315-2330 _check_match: is (body, geom), one side of a contact, the sensor's object

@@ -451,7 +451,7 @@ _OPTIONAL_FIELDS = {
     """mat_rgba mesh_vertadr mesh_vertnum mesh_vert mesh_face mesh_faceadr mesh_graph mesh_polyadr mesh_polynormal mesh_polyvertadr
     mesh_polyvertnum mesh_polyvert mesh_polymapadr mesh_polymapnum mesh_polymap hfield_size hfield_nrow hfield_ncol hfield_adr hfield_data
     sensor_type sensor_datatype sensor_objtype sensor_objid sensor_reftype sensor_refid sensor_dim sensor_adr sensor_cutoff
-    sensor_intprm sensor_contact_adr
+    sensor_intprm sensor_contact_adr sensor_collision_adr
     pair_dim pair_friction pair_solref pair_solreffriction pair_solimp pair_margin pair_gap site_bodyid site_pos site_quat
     eq_obj1id eq_obj2id eq_solref eq_solimp eq_data""".split()),
 }
@@ -486,7 +486,7 @@ def _sensor_facts(sensor_type):
     warnings.warn(f"sensor types {sorted(set(bad))} are not computed by this engine (csrc/sensor.hpp computes {sorted(supported)}): their sensordata entries are 0")
   count = lambda kinds: int(sum(int(t) in kinds for t in sensor_type))
   return dict(nsensor_acc=count((0, 1, 4, 5, 22, 33, 34, 42)), nsensor_energy=count((43, 44)), nsensor_frc=count((4, 5)), nsensor_subtree=count((36, 37)),
-              nsensor_contact=count((42,)))
+              nsensor_contact=count((42,)), nsensor_collision=count((39, 40, 41)))
 
 
 CONTACT_SENSOR_MAXMATCH_CAP = 64  # csrc/sensor_contact.hpp: one wavefront per world, lane k owns match k
@@ -536,6 +536,50 @@ def _contact_sensor_tables(host, nsensor_contact):
   return dict(sensor_intprm=np.ascontiguousarray(intprm, dtype=np.int32), sensor_contact_adr=np.concatenate([ids, np.full(n - len(ids), -1, dtype=np.int32)]))
 
 
+def _body_geoms(mjm, nbody):
+  """body_geomnum / body_geomadr [nbody] from geom_bodyid (a body's geoms are contiguous, MuJoCo's order; adr -1 for a body without geoms):
+  the same tables MuJoCo compiles, without asking the host model for them."""
+  bodyid = _arr(mjm.geom_bodyid, np.int32).reshape(-1)
+  if len(bodyid) and (np.diff(bodyid) < 0).any():
+    raise ValueError("geoms must be ordered by body (MuJoCo order)")
+  num = np.bincount(bodyid, minlength=nbody).astype(np.int32)
+  first = np.searchsorted(bodyid, np.arange(nbody)).astype(np.int32)
+  return dict(body_geomnum=num, body_geomadr=np.where(num > 0, first, -1).astype(np.int32))
+
+
+def _collision_sensor_tables(host, names=None):
+  """sensor_collision_adr [nsensor] of the model whose other tables are in `host`; checks what csrc/sensor_collision.hpp relies on and
+  refuses the geom pairs it does not serve."""
+  stype, n = host["sensor_type"], len(host["sensor_type"])
+  ids = np.flatnonzero((stype >= 39) & (stype <= 41)).astype(np.int32)
+  nbody, ngeom = len(host["body_parentid"]), len(host["geom_bodyid"])
+  gtype, dataid, vertnum = host["geom_type"], host["geom_dataid"], host["mesh_vertnum"]
+  PLANE, HFIELD, MESH = int(types.GeomType.PLANE), int(types.GeomType.HFIELD), int(types.GeomType.MESH)
+  for i in ids:
+    sides = []
+    who = f"geom distance sensor {i}" + (f" {names[i]!r}" if names is not None and len(names) > i and names[i] else "")
+    for which in ("obj", "ref"):
+      t, k = int(host[f"sensor_{which}type"][i]), int(host[f"sensor_{which}id"][i])
+      if t not in (1, 5) or not 0 <= k < (nbody if t == 1 else ngeom):
+        raise ValueError(f"{who}: sensor_{which}type {t} / sensor_{which}id {k} is not a body or geom of the model")
+      adr, num = (int(host["body_geomadr"][k]), int(host["body_geomnum"][k])) if t == 1 else (k, 1)
+      if num > 0 and not (0 <= adr and adr + num <= ngeom):
+        raise ValueError(f"{who}: body {k} has geoms {adr}..{adr + num - 1} outside the model's {ngeom}")
+      sides.append(range(adr, adr + num))
+    if int(host["sensor_dim"][i]) != {39: 1, 40: 3, 41: 6}[int(stype[i])]:
+      raise ValueError(f"{who}: sensor_dim {int(host['sensor_dim'][i])} does not agree with sensor type {int(stype[i])}")
+    if float(host["sensor_cutoff"][i]) < 0.0:
+      raise ValueError(f"{who}: negative cutoff")
+    for g in (*sides[0], *sides[1]):
+      if gtype[g] == HFIELD:
+        raise NotImplementedError(f"{who}: height-field geom {g} (distance to a height field is not implemented)")
+      if gtype[g] == MESH and (dataid[g] < 0 or dataid[g] >= len(vertnum) or vertnum[dataid[g]] <= 0):
+        raise NotImplementedError(f"{who}: mesh geom {g} has no vertices")
+    if any(gtype[a] == PLANE for a in sides[0]) and any(gtype[b] == PLANE for b in sides[1]):
+      raise NotImplementedError(f"{who}: a plane-plane pair (distance between two planes is not implemented)")
+  return dict(sensor_collision_adr=np.concatenate([ids, np.full(n - len(ids), -1, dtype=np.int32)]))
+
+
 def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   """Creates a model on device (reference io.py:259).
 
@@ -560,6 +604,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     host.update(arrays)
   o, s, arrays = _options(mjm, m)
   host.update(arrays)
+  host.update(_body_geoms(mjm, m.nbody))
   sizes = {k: v for k, v in vars(m).items() if isinstance(v, int) and not k.startswith("_")}
   for name in _MODEL_PTR_FIELDS:
     if name not in host:
@@ -569,6 +614,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   for name, value in {**_sensor_facts(host["sensor_type"]), **_ray_facts(host)}.items():
     setattr(m, name, value)
   host.update(_contact_sensor_tables(host, m.nsensor_contact))
+  host.update(_collision_sensor_tables(host, getattr(mjm, "sensor_names", None)))
   m.sleep_enabled = int(bool(int(opt.enableflags) & int(types.EnableBit.SLEEP)) and not (int(opt.disableflags) & int(types.DisableBit.ISLAND)))
   m.opt_sleep_tolerance = float(getattr(opt, "sleep_tolerance", 1e-4))
   if m.sleep_enabled and (host["tree_sleep_policy"] > int(types.SleepPolicy.AUTO_ALLOWED)).any():

@@ -1580,10 +1580,11 @@ def _compile(root, base_dir):
 # mjtSensor / mjtObj / mjtDataType / mjtStage values used below (MuJoCo's enums; UNPINNED here -- the mujoco package is absent: a real
 # MjModel carries its own numbers in sensor_type, which put_model compares with these)
 SENS = {"touch": 0, "accelerometer": 1, "force": 4, "torque": 5, "magnetometer": 6, "jointactuatorfrc": 16, "jointlimitpos": 20, "jointlimitvel": 21, "jointlimitfrc": 22, "e_potential": 43, "e_kinetic": 44, "framelinacc": 33, "frameangacc": 34, "velocimeter": 2, "gyro": 3, "jointpos": 9, "jointvel": 10, "actuatorpos": 13, "actuatorvel": 14, "actuatorfrc": 15, "ballquat": 18, "ballangvel": 19,
-        "framepos": 26, "framequat": 27, "framexaxis": 28, "frameyaxis": 29, "framezaxis": 30, "framelinvel": 31, "frameangvel": 32, "subtreecom": 35, "subtreelinvel": 36, "subtreeangmom": 37, "clock": 45, "rangefinder": 7, "contact": 42}
+        "framepos": 26, "framequat": 27, "framexaxis": 28, "frameyaxis": 29, "framezaxis": 30, "framelinvel": 31, "frameangvel": 32, "subtreecom": 35, "subtreelinvel": 36, "subtreeangmom": 37, "clock": 45, "rangefinder": 7, "contact": 42,
+        "insidesite": 38, "distance": 39, "normal": 40, "fromto": 41}
 # sensors that keep their slot in sensordata (the reference's layout) but are not computed: the engine writes zeros and put_model warns
 SENS_UNSUPPORTED = {}
-_SENS_DIM = {"touch": 1, "rangefinder": 1, "ballquat": 4, "framequat": 4, "jointactuatorfrc": 1, "jointlimitpos": 1, "jointlimitvel": 1, "jointlimitfrc": 1, "e_potential": 1, "e_kinetic": 1, "jointpos": 1, "jointvel": 1, "actuatorpos": 1, "actuatorvel": 1, "actuatorfrc": 1, "clock": 1}
+_SENS_DIM = {"touch": 1, "rangefinder": 1, "ballquat": 4, "framequat": 4, "jointactuatorfrc": 1, "jointlimitpos": 1, "jointlimitvel": 1, "jointlimitfrc": 1, "e_potential": 1, "e_kinetic": 1, "jointpos": 1, "jointvel": 1, "actuatorpos": 1, "actuatorvel": 1, "actuatorfrc": 1, "clock": 1, "insidesite": 1, "distance": 1, "normal": 3, "fromto": 6}
 _SENS_STAGE = {"velocimeter": 2, "gyro": 2, "jointvel": 2, "actuatorvel": 2, "ballangvel": 2, "framelinvel": 2, "frameangvel": 2, "subtreelinvel": 2, "subtreeangmom": 2, "jointlimitvel": 2, "e_kinetic": 2, "touch": 3, "jointlimitfrc": 3, "jointactuatorfrc": 3, "actuatorfrc": 3, "accelerometer": 3, "force": 3, "torque": 3, "framelinacc": 3, "frameangacc": 3, "contact": 3}  # default: POS (1)
 _OBJ = {"body": 1, "xbody": 2, "geom": 5, "site": 6, "camera": 7}
 # <contact> sensor (mjSENS_CONTACT): the data fields in their canonical order with the floats each takes in a slot -- bit i of
@@ -1627,9 +1628,50 @@ def _contact_sensor(a, lookup):
   return objtype, objid, reftype, refid, (dataspec, CONTACT_REDUCE[a.get("reduce", "none")], num), num * contact_slot_size(dataspec)
 
 
+def _geomdist_sensor(tag, a, lookup):
+  """(objtype, objid, reftype, refid) of a <distance> / <normal> / <fromto> element: each side one geom or one body (its own geoms)."""
+  who = f"sensor <{tag}> {a.get('name', '')!r}"
+  def side(k, what):
+    given = [n for n in (f"geom{k}", f"body{k}") if n in a]
+    if len(given) != 1:
+      raise ValueError(f"{who}: exactly one of geom{k} / body{k} ({what} object), got {given}")
+    objtype = 5 if given[0].startswith("geom") else 1
+    if a[given[0]] not in lookup[objtype]:
+      raise ValueError(f"{who}: unknown {given[0]} {a[given[0]]!r}")
+    return objtype, lookup[objtype].index(a[given[0]])
+  objtype, objid = side(1, "first")
+  reftype, refid = side(2, "second")
+  if (objtype, objid) == (reftype, refid):
+    raise ValueError(f"{who}: both sides name the same {'geom' if objtype == 5 else 'body'}")
+  if float(a.get("cutoff", 0.0)) < 0.0:
+    raise ValueError(f"{who}: cutoff must not be negative")
+  return objtype, objid, reftype, refid
+
+
+def _insidesite_sensor(m, a, lookup):
+  """(objtype, objid, reftype, refid) of an <insidesite> element: is the object's position inside the volume of `site`."""
+  who = f"sensor <insidesite> {a.get('name', '')!r}"
+  if a.get("objtype") == "camera":
+    raise NotImplementedError(f"{who}: objtype camera is not implemented (the engine has no camera frames: Model.ncam is 0)")
+  if a.get("objtype") not in ("body", "xbody", "geom", "site"):
+    raise ValueError(f"{who}: objtype must be one of body, xbody, geom, site, got {a.get('objtype')!r}")
+  objtype = _OBJ[a["objtype"]]
+  if a.get("objname") not in lookup[objtype] or a.get("site") not in lookup[6]:
+    raise ValueError(f"{who}: unknown objname {a.get('objname')!r} or site {a.get('site')!r}")
+  objid = lookup[objtype].index(a["objname"])
+  if objtype == 1 and objid > 0:  # (reference sensor.py:724-733 reads subtree_com for such a body)
+    sub = np.array(m.body_mass, dtype=np.float64)
+    for b in range(len(sub) - 1, 0, -1):
+      sub[m.body_parentid[b]] += sub[b]
+    if m.body_mass[objid] < MJ_MINVAL and sub[objid] >= MJ_MINVAL:
+      raise NotImplementedError(f"{who}: a massless body with a massive subtree as objtype body is not implemented (use xbody)")
+  return objtype, objid, 6, lookup[6].index(a["site"])
+
+
 def _compile_sensors(m, root, site_names):
-  """<sensor> section, the subset csrc/sensor.hpp and csrc/sensor_contact.hpp compute (reference sensor.py: joint / actuator / ball / frame /
-  IMU-style site sensors, subtree centre of mass, clock, contact); anything else raises."""
+  """<sensor> section, the subset csrc/sensor.hpp, csrc/sensor_contact.hpp and csrc/sensor_collision.hpp compute (reference sensor.py: joint /
+  actuator / ball / frame / IMU-style site sensors, subtree centre of mass, clock, contact, geom distance / normal / fromto, insidesite);
+  anything else raises."""
   rows = []
   lookup = {1: m.body_names, 2: m.body_names, 5: m.geom_names, 6: site_names}
   for sec in root.findall("sensor"):
@@ -1644,6 +1686,10 @@ def _compile_sensors(m, root, site_names):
       objtype, objid, reftype, refid, intprm, dim = 0, -1, 0, -1, (0, 0, 0), _SENS_DIM.get(e.tag, 3)
       if e.tag == "contact":
         objtype, objid, reftype, refid, intprm, dim = _contact_sensor(a, lookup)
+      elif e.tag in ("distance", "normal", "fromto"):
+        objtype, objid, reftype, refid = _geomdist_sensor(e.tag, a, lookup)
+      elif e.tag == "insidesite":
+        objtype, objid, reftype, refid = _insidesite_sensor(m, a, lookup)
       elif e.tag in ("jointactuatorfrc", "jointlimitpos", "jointlimitvel", "jointlimitfrc"):
         objtype, objid = 3, m.jnt_names.index(a["joint"])
       elif e.tag in ("jointpos", "jointvel", "ballquat", "ballangvel"):
@@ -1663,7 +1709,7 @@ def _compile_sensors(m, root, site_names):
         if "reftype" in a:
           reftype = _OBJ[a["reftype"]]
           refid = lookup[reftype].index(a["refname"])
-      rows.append(dict(type=SENS[e.tag], datatype=1 if e.tag == "touch" else 3 if e.tag in ("ballquat", "framequat") else (2 if e.tag.startswith("frame") and e.tag.endswith("axis") else 0),
+      rows.append(dict(type=SENS[e.tag], datatype=1 if e.tag == "touch" else 3 if e.tag in ("ballquat", "framequat") else (2 if (e.tag.startswith("frame") and e.tag.endswith("axis")) or e.tag == "normal" else 0),
                        needstage=_SENS_STAGE.get(e.tag, 1), objtype=objtype, objid=objid, reftype=reftype, refid=refid, dim=dim,
                        cutoff=float(a.get("cutoff", 0.0)), name=a.get("name", ""), intprm=intprm))
   m.nsensor = len(rows)

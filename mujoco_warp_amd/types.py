@@ -232,6 +232,49 @@ class ContactType(enum.IntFlag):
   SENSOR = 2
 
 
+class SensorType(enum.IntEnum):
+  """mjtSensor values of the sensors this engine computes (the loader's table mjcf.SENS holds the same numbers by element name)."""
+  TOUCH = 0
+  ACCELEROMETER = 1
+  VELOCIMETER = 2
+  GYRO = 3
+  FORCE = 4
+  TORQUE = 5
+  MAGNETOMETER = 6
+  RANGEFINDER = 7
+  JOINTPOS = 9
+  JOINTVEL = 10
+  ACTUATORPOS = 13
+  ACTUATORVEL = 14
+  ACTUATORFRC = 15
+  JOINTACTFRC = 16
+  BALLQUAT = 18
+  BALLANGVEL = 19
+  JOINTLIMITPOS = 20
+  JOINTLIMITVEL = 21
+  JOINTLIMITFRC = 22
+  FRAMEPOS = 26
+  FRAMEQUAT = 27
+  FRAMEXAXIS = 28
+  FRAMEYAXIS = 29
+  FRAMEZAXIS = 30
+  FRAMELINVEL = 31
+  FRAMEANGVEL = 32
+  FRAMELINACC = 33
+  FRAMEANGACC = 34
+  SUBTREECOM = 35
+  SUBTREELINVEL = 36
+  SUBTREEANGMOM = 37
+  INSIDESITE = 38
+  GEOMDIST = 39
+  GEOMNORMAL = 40
+  GEOMFROMTO = 41
+  CONTACT = 42
+  E_POTENTIAL = 43
+  E_KINETIC = 44
+  CLOCK = 45
+
+
 MJ_MINVAL = 1e-15
 MJ_MAXVAL = 1e10
 MJ_MINIMP = 0.0001
@@ -493,6 +536,11 @@ class Model(_Dirty):
   sensor_dim: DeviceArray = _arr(('nsensor',), "int32")
   sensor_adr: DeviceArray = _arr(('nsensor',), "int32")
   sensor_cutoff: DeviceArray = _arr(('nsensor',), "float32")
+  # geom distance sensors, types 39..41 (csrc/sensor_collision.hpp; reference types.py Model.sensor_collision_adr)
+  nsensor_collision: int = 0
+  sensor_collision_adr: DeviceArray = _arr(('nsensor',), "int32")  # ids of the distance / normal / fromto sensors first, -1 after them
+  body_geomnum: DeviceArray = _arr(('nbody',), "int32")  # the geoms of a body (a sensor side that names a body ranges over them)
+  body_geomadr: DeviceArray = _arr(('nbody',), "int32")
   # contact sensors (csrc/sensor_contact.hpp; reference types.py Model.sensor_intprm / sensor_contact_adr)
   nsensor_contact: int = 0
   sensor_intprm: DeviceArray = _arr(('nsensor', 3), "int32")  # contact sensors: dataspec bits, reduce, num; 0 elsewhere
