@@ -237,6 +237,21 @@ typedef struct MjhModel {
   const float* actuator_forcerange; int actuator_forcerange_nb;
   const float* actuator_actrange; int actuator_actrange_nb;
   const float* actuator_gear; int actuator_gear_nb;
+  /* general transmissions (csrc/transmission.hpp; an addition within ABI v45 that is NOT at the tail: the offsets of every later field move).
+     actuator_trnid above is what the single-dof kernels index jnt_dofadr / jnt_qposadr with: the target joint of a hinge / slide row and, for
+     every other row, the joint of the row's first dof (joint 0 for an empty row) -- always a valid joint; the targets themselves are in
+     actuator_trnobj.  With trn_general == 0 the two are equal and none of the other fields is read. */
+  int trn_general;              /* 1: some actuator's moment row is not the scalar gear[0] of a hinge / slide joint: k_transmission runs behind the
+                                   position stage and the velocity stage takes its general instantiation (sparse moment rows) */
+  int nJmom;                    /* entries of all moment rows (reference types.py Model.nJmom); nu when trn_general == 0 */
+  const int* actuator_trntype;  /* [nu] TrnType: 0 joint, 1 jointinparent, 4 site */
+  const int* actuator_trnobj;   /* [nu, 2] Model.actuator_trnid: joint | site, refsite or -1 */
+  const int* moment_rownnz; const int* moment_rowadr; /* [nu] the rows of Data.actuator_moment [nworld, nJmom], actuator order */
+  const int* moment_colind;     /* [nJmom] dof of each entry, ascending within a row */
+  const int* moment_rowid;      /* [nJmom] actuator of each entry (k_transmission: one lane per entry) */
+  const int* moment_side;       /* [nJmom] site rows: 1 the dof moves the site only, 2 the refsite only (its entry is subtracted); 0 joint rows */
+  const int* momentT_adr;       /* [nv + 1] the transpose, dof-major: dof i owns entries momentT_adr[i] .. momentT_adr[i + 1] of */
+  const int* momentT_act; const int* momentT_ind; /* [nJmom] actuator and index into its world's actuator_moment, ascending actuator */
   /* equality constraints: joint couplings only (constraint.py:500-640); eq_data = polycoef[0..4] */
   const int* eq_obj1id; const int* eq_obj2id;
   const float* eq_solref; int eq_solref_nb;
@@ -262,7 +277,7 @@ typedef struct MjhData {
   float* xpos; float* xquat; float* xmat; float* xipos; float* ximat; float* xanchor; float* xaxis;
   float* geom_xpos; float* geom_xmat; float* site_xpos; float* site_xmat;
   float* subtree_com; float* cinert; float* cdof; float* crb; float* M; float* qLD; float* qLDiagInv;
-  float* actuator_length; float* actuator_moment;
+  float* actuator_length; float* actuator_moment; /* [nworld, nu], [nworld, nJmom] (sparse rows: MjhModel.moment_*; written only when trn_general) */
   /* velocity-dependent */
   float* actuator_velocity; float* cvel; float* cdof_dot;
   float* qfrc_spring; float* qfrc_damper; float* qfrc_gravcomp; float* qfrc_passive; float* qfrc_bias;

@@ -11,6 +11,7 @@
 //   set_const_tu.hip (k_set_const and its entry point mjh_set_const: the derived model constants),
 //   sensor_contact_tu.hip (k_sensor_contact: the contact sensors behind the acceleration-stage sensor launch),
 //   sensor_collision_tu.hip (k_sensor_collision: the geom distance sensors behind the position-stage sensor launch),
+//   transmission_tu.hip (k_transmission, k_fwd_vel_trn: general actuator transmissions, only for models with MjhModel.trn_general),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
@@ -171,3 +172,7 @@ int launch_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc,
 int launch_sensor_contact(const MjhModel* m, const MjhData* d, hipStream_t s);
 // geom distance sensors (sensor_collision.hpp, sensor_collision_tu.hip): one wavefront per (world, sensor), after k_sensor of the position stage
 int launch_sensor_collision(const MjhModel* m, const MjhData* d, hipStream_t s);
+// general actuator transmissions (transmission.hpp, transmission_tu.hip; MjhModel.trn_general): actuator_length / actuator_moment behind the position
+// stage, and the velocity stage's instantiation that reads the sparse moment rows (lanes64: the caller's lane choice for the model)
+int launch_transmission(const MjhModel* m, const MjhData* d, hipStream_t s);
+int launch_vel_trn(const MjhModel* m, const MjhData* d, int first, int last, bool lanes64, hipStream_t s);

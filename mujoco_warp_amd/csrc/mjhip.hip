@@ -154,7 +154,13 @@ static int launch_vel_g(const MjhModel* m, const MjhData* d, int first, int last
   const VelLayout lay = vel_layout(m->nq, m->nv, m->nbody, m->nC, m->nu);
   return launch_per_world(k_fwd_vel<G>, "k_fwd_vel: model does not fit in LDS", G, sizeof(int) * mstruct_ints(m->nv, m->nC), sizeof(float) * lay.total, d->nworld, s, *m, *d, first, last);
 }
-static int launch_vel(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) { return lanes64(m) ? launch_vel_g<64>(m, d, first, last, s) : launch_vel_g<32>(m, d, first, last, s); }
+// (general transmissions, MjhModel.trn_general: the velocity stage's TRN instantiation and k_transmission behind the position stage, both in
+// transmission_tu.hip -- every other model launches what it launched before)
+static int launch_vel(const MjhModel* m, const MjhData* d, int first, int last, hipStream_t s) {
+  if (m->trn_general) return launch_vel_trn(m, d, first, last, lanes64(m), s);
+  return lanes64(m) ? launch_vel_g<64>(m, d, first, last, s) : launch_vel_g<32>(m, d, first, last, s);
+}
+static int launch_trn(const MjhModel* m, const MjhData* d, hipStream_t s) { return m->trn_general ? launch_transmission(m, d, s) : MJH_OK; }
 // public L'DL factor (qLD, qLDiagInv) and, on request, qacc_smooth: outputs nobody inside the step waits for
 // (32 lanes per world here and in the other kernels that chain over the sparse factor -- k_integrate, k_integrate_plus, k_solve_m, and
 // k_publish_contacts with them: more lanes per world only halve the worlds per wavefront)
@@ -775,7 +781,7 @@ static int run_sleep_step(const MjhModel* m, const MjhData* d, bool step, hipStr
   if (step && m->integrator == INT_RK4) return fail(MJH_E_UNSUPPORTED, "sleeping with the RK4 integrator");
   const int mode = integrator_mode(m);
   { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE, s)); }
-  { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); }
+  { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); TRY(launch_trn(m, d, s)); }
   { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
   { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE_COLLISION, s)); }
   {
@@ -830,7 +836,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
     case MJH_STAGE_MAKE_CONSTRAINT:
       { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
       { Scope sc(K_OTHER); return launch_publish(m, d, s); }
-    case MJH_STAGE_TRANSMISSION: return MJH_OK;  // joint transmissions: length/moment are produced by fwd_actuation
+    case MJH_STAGE_TRANSMISSION: { Scope sc(K_POS); return launch_trn(m, d, s); }  // (hinge / slide scalar rows only: the length is produced by fwd_actuation)
     case MJH_STAGE_COM_VEL: { Scope sc(K_VEL); return launch_vel(m, d, VEL_COMVEL, VEL_COMVEL, s); }
     case MJH_STAGE_PASSIVE: { Scope sc(K_VEL); return launch_vel(m, d, VEL_PASSIVE, VEL_PASSIVE, s); }
     case MJH_STAGE_RNE: { Scope sc(K_VEL); return launch_vel(m, d, VEL_RNE, VEL_RNE, s); }
@@ -843,7 +849,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
     case MJH_STAGE_EULER: { Scope sc(K_INTEGRATE); return launch_integrate(m, d, 0, s); }
     case MJH_STAGE_IMPLICIT: { Scope sc(K_INTEGRATE); return launch_integrate(m, d, m->integrator == INT_IMPLICIT ? 2 : 1, s); }
     case MJH_STAGE_FWD_POSITION:
-      { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_FACTOR, s)); }
+      { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_FACTOR, s)); TRY(launch_trn(m, d, s)); }
       { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
       { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
       { Scope sc(K_OTHER); TRY(launch_publish(m, d, s)); }
@@ -907,7 +913,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         // profiling pass: one plain kernel per stage, so that the event pairs time one kernel at a time
         const int mode = integrator_mode(m);
         { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, sched_cls_host(*m, *d)); }
-        { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); }
+        { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); TRY(launch_trn(m, d, s)); }
         { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
         { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
         { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
@@ -926,7 +932,17 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
       if (p.riders == RIDE_SIDE && !side) p = plan_step(m, d, stage, instrumented, false);  // (a failing device: the riders go with the integrator launch)
       bool sched_done = false;
       { Scope sc(K_POS); TRY(launch_pos_plus(m, d, POS_KINEMATICS, POS_CRB, &sched_done, s)); }
-      { Scope sc(K_MID); TRY(launch_mid(m, d, !sched_done, s)); }
+      if (m->trn_general) {
+        // k_mid's velocity-stage role is the default instantiation: such a model takes the roles as launches of their own, behind k_transmission
+        { Scope sc(K_POS); TRY(launch_trn(m, d, s)); }
+        if (!sched_done) { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, sched_cls_host(*m, *d)); }
+        { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
+        { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
+        { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
+      } else {
+        Scope sc(K_MID);
+        TRY(launch_mid(m, d, !sched_done, s));
+      }
       { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s)); }  // (no launch without sensors; before the solver, whose epilogue may integrate the state)
       if (side) {
         // (tried in round 3: forking the factor after k_fwd_pos, beside k_mid, with qacc_smooth as a separate solve after k_mid -- humanoid

@@ -811,7 +811,18 @@ DEV float jac_dot(const MjhModel& m, const float* cdof_i, V3 offset, V3 force, V
   return dot(lin + cross(ang, offset), force) + dot(ang, torque);
 }
 
-template <int G>
+// TRN (compile time): the general transmission path (csrc/transmission.hpp k_fwd_vel_trn, models with MjhModel.trn_general) -- sparse moment
+// rows written by k_transmission instead of the hinge / slide scalar gear[0]: actuator_velocity = moment . qvel over the row,
+// qfrc_actuator = moment' force gathered per dof over the transpose lists (one lane per dof, fixed order, no atomics).  The default
+// instantiation is the one every other model launches; its code does not depend on the switch.
+DEV float trn_row_dot(const MjhModel& m, const MjhData& d, int w, int u, const float* qvel) {
+  const float* mom = d.actuator_moment + (size_t)w * m.nJmom;
+  const int adr = m.moment_rowadr[u], n = m.moment_rownnz[u];
+  float s = 0.0f;
+  for (int k = adr; k < adr + n; ++k) s += mom[k] * qvel[m.moment_colind[k]];
+  return s;
+}
+template <int G, bool TRN = false>
 DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, float* smem, const Blk& b) {
   if ((int)threadIdx.x >= b.nthreads) return;
   const int nq = m.nq, nv = m.nv, nbody = m.nbody, njnt = m.njnt, nC = m.nC, nu = m.nu;
@@ -876,9 +887,13 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
       }
       for (int k = 0; k < 6; ++k) cvel[6 * b + k] = cv[k];
     }
-    const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
-    for (int u = lig; u < nu; u += G)
-      d.actuator_velocity[(size_t)w * nu + u] = gear[6 * u] * qvel[m.jnt_dofadr[m.actuator_trnid[2 * u]]];
+    if constexpr (TRN) {
+      for (int u = lig; u < nu; u += G) d.actuator_velocity[(size_t)w * nu + u] = trn_row_dot(m, d, w, u, qvel);
+    } else {
+      const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
+      for (int u = lig; u < nu; u += G)
+        d.actuator_velocity[(size_t)w * nu + u] = gear[6 * u] * qvel[m.jnt_dofadr[m.actuator_trnid[2 * u]]];
+    }
     gsync();
     gcopy<G>(d.cvel + (size_t)w * 6 * nbody, cvel, 6 * nbody, lig);
     gcopy<G>(d.cdof_dot + (size_t)w * 6 * nv, cdof_dot, 6 * nv, lig);
@@ -1022,9 +1037,15 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
           d.act_dot[(size_t)w * m.na + adr] = act_dot;
           ctrl_act = act;
         }
-        const int jid = m.actuator_trnid[2 * u];
-        const float length = qpos[m.jnt_qposadr[jid]] * gear[6 * u];
-        const float velocity = gear[6 * u] * qvel[m.jnt_dofadr[jid]];
+        float length, velocity;
+        if constexpr (TRN) {  // (the length is k_transmission's, behind the position stage)
+          length = d.actuator_length[(size_t)w * nu + u];
+          velocity = trn_row_dot(m, d, w, u, qvel);
+        } else {
+          const int jid = m.actuator_trnid[2 * u];
+          length = qpos[m.jnt_qposadr[jid]] * gear[6 * u];
+          velocity = gear[6 * u] * qvel[m.jnt_dofadr[jid]];
+        }
         const float* gp = bf(m.actuator_gainprm, m.actuator_gainprm_nb, w, 10 * nu) + 10 * u;
         const float* bp = bf(m.actuator_biasprm, m.actuator_biasprm_nb, w, 10 * nu) + 10 * u;
         const float gain = m.actuator_gaintype[u] == 0 ? gp[0] : gp[0] + gp[1] * length + gp[2] * velocity;
@@ -1034,7 +1055,7 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
           const float* fr = bf(m.actuator_forcerange, m.actuator_forcerange_nb, w, 2 * nu) + 2 * u;
           force = clampf(force, fr[0], fr[1]);
         }
-        d.actuator_length[(size_t)w * nu + u] = length;
+        if constexpr (!TRN) d.actuator_length[(size_t)w * nu + u] = length;
       }
       d.actuator_force[(size_t)w * nu + u] = force;
       uforce[u] = force;
@@ -1044,7 +1065,16 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
     // actuators (nv x nu dependent table loads: it was 28 % of this kernel on the humanoid, 48 % on three of them)
     for (int i = lig; i < nv; i += G) factuator[i] = 0.0f;
     gsync();
-    if (!(dsbl & DSBL_ACTUATION)) {
+    if constexpr (TRN) {
+      if (!(dsbl & DSBL_ACTUATION)) {
+        const float* mom = d.actuator_moment + (size_t)w * m.nJmom;
+        for (int i = lig; i < nv; i += G) {
+          float s = 0.0f;
+          for (int k = m.momentT_adr[i]; k < m.momentT_adr[i + 1]; ++k) s += mom[m.momentT_ind[k]] * uforce[m.momentT_act[k]];
+          factuator[i] = s;
+        }
+      }
+    } else if (!(dsbl & DSBL_ACTUATION)) {
       if (m.act_dof_max <= 2) {
         for (int u = lig; u < nu; u += G) atomicAdd(&factuator[m.jnt_dofadr[m.actuator_trnid[2 * u]]], gear[6 * u] * uforce[u]);
       } else {

@@ -19,6 +19,7 @@ from typing import Optional
 import numpy as np
 
 from . import _abi
+from . import trn_tables as transmission
 from . import types
 from .device import DeviceArray
 
@@ -214,14 +215,10 @@ def _check_supported(mjm, pairs):
     raise NotImplementedError(f"Unknown solver {int(opt.solver)}.")
   if int(opt.cone) not in (types.ConeType.PYRAMIDAL, types.ConeType.ELLIPTIC):
     raise NotImplementedError(f"Unknown cone {int(opt.cone)}.")
-  if mjm.nu and (np.asarray(mjm.actuator_trntype) != types.TrnType.JOINT).any():
-    raise NotImplementedError("Only joint transmissions are supported.")
   if mjm.nu:
-    # the kernels use gear[0], qpos[jnt_qposadr] and the joint's first dof only (smooth.hpp fwd_actuation, integrate.hpp): a
-    # motor on a ball / free joint (gear[0:3] / gear[0:6] in the reference, smooth.py:2288-2400) would silently be wrong
-    tj = np.asarray(mjm.jnt_type)[np.asarray(mjm.actuator_trnid).reshape(-1, 2)[:, 0]]
-    if np.isin(tj, (int(types.JointType.BALL), int(types.JointType.FREE))).any():
-      raise NotImplementedError("actuators on ball / free joints are not implemented (hinge and slide targets only).")
+    transmission.check_types(mjm.actuator_trntype)  # (joint, jointinparent and site; body / slider-crank / tendon are refused by name)
+    if not mjm.nv:
+      raise NotImplementedError("actuators on a model without degrees of freedom are not implemented.")
   if int(getattr(opt, "noslip_iterations", 0)) > 0:
     raise NotImplementedError("noslip solver is unsupported.")
   if mjm.nu:
@@ -427,18 +424,56 @@ def _tree_tables(mjm):
                      dof_treeid=dof_treeid, body_treeid=body_treeid)
 
 
+def _check_trn_feedback(trn_feedback, integrator):
+  """The kernels that differentiate the actuator force (csrc/integrate.hpp, implicit.hpp, solver.hpp) take one dof per actuator: velocity
+  feedback on a multi-dof moment row is refused with the implicit integrators -- at put_model and again when the C struct is built,
+  because opt.integrator is read live."""
+  if trn_feedback and integrator in (int(types.IntegratorType.IMPLICITFAST), int(types.IntegratorType.IMPLICIT)):
+    raise NotImplementedError(f"velocity feedback (an affine gain or bias with a velocity coefficient) on a multi-dof transmission with the "
+                              f"{types.IntegratorType(integrator).name.lower()} integrator: the implicit integrators differentiate single-dof rows only; "
+                              "use Euler or RK4")
+  return integrator
+
+
 def _actuator_facts(mjm):
-  """act_dof_max and act_velfeedback."""
+  """(facts, host arrays) of the actuators: act_dof_max and act_velfeedback of the single-dof kernels, and the transmission tables of
+  csrc/transmission.hpp -- the static sparse structure of Data.actuator_moment (rows in actuator order, columns ascending), its dof-major
+  transpose and trn_general, which is 0 exactly when every row is the scalar gear[0] of a hinge / slide joint."""
   nv, nu = int(mjm.nv), int(mjm.nu)
+  i32 = lambda n=0, *rest: np.zeros((n, *rest), dtype=np.int32)
   if not nu:
-    return dict(act_dof_max=0, act_velfeedback=0)
-  adof = np.asarray(mjm.jnt_dofadr)[np.asarray(mjm.actuator_trnid).reshape(-1, 2)[:, 0]]
+    return dict(act_dof_max=0, act_velfeedback=0, trn_general=0, nJmom=0, trn_feedback=0), dict(
+      actuator_trntype=i32(), actuator_trnobj=i32(0, 2), actuator_trnjnt=i32(0, 2), moment_rownnz=i32(), moment_rowadr=i32(), moment_colind=i32(),
+      moment_side=i32(), moment_rowid=i32(), momentT_adr=i32(nv + 1), momentT_act=i32(), momentT_ind=i32())
+  trntype = _arr(mjm.actuator_trntype, np.int32).reshape(nu)
+  tid = _arr(mjm.actuator_trnid, np.int32).reshape(nu, 2)
+  for u in range(nu):  # (the kernels index the joint / site tables with these)
+    site = trntype[u] == types.TrnType.SITE
+    count = int(getattr(mjm, "nsite", 0)) if site else int(mjm.njnt)
+    if not 0 <= tid[u, 0] < count or (site and not -1 <= tid[u, 1] < count):
+      raise ValueError(f"actuator {u}: actuator_trnid {tid[u].tolist()} does not name a {'site' if site else 'joint'} of the model")
+  st = transmission.moment_structure(mjm)
+  scalar = st.pop("scalar")
+  nJmom = st.pop("nJmom")
+  trnid = _arr(mjm.actuator_trnid, np.int32).reshape(nu, 2)
+  # what the single-dof kernels (integrate.hpp, implicit.hpp, solver.hpp: d qfrc_actuator / d qvel) index jnt_dofadr with: the target joint
+  # of a scalar row; for any other row -- which contributes nothing there, see the refusal below -- the joint of its first dof (0 if empty)
+  first, has = np.zeros(nu, dtype=np.int64), st["moment_rownnz"] > 0
+  first[has] = st["moment_colind"][st["moment_rowadr"][has]]
+  trnjnt = trnid.copy()
+  trnjnt[~scalar, 0] = _arr(mjm.dof_jntid, np.int32).reshape(-1)[first[~scalar]]
+  trnjnt[~scalar, 1] = -1
+  adof = np.asarray(mjm.jnt_dofadr)[trnid[scalar, 0]]
   # d(force)/d(velocity) of an actuator = gainprm[2] * ctrl (affine gain) + biasprm[2] (affine bias): non-positive for every ctrl only
   # without a gain term and with biasprm[2] <= 0 (a position servo's -kv); otherwise the implicitfast matrix can lose definiteness
   gp, bp = np.asarray(mjm.actuator_gainprm, dtype=np.float64).reshape(nu, -1), np.asarray(mjm.actuator_biasprm, dtype=np.float64).reshape(nu, -1)
   gt, bt = np.asarray(mjm.actuator_gaintype).reshape(-1), np.asarray(mjm.actuator_biastype).reshape(-1)
-  return dict(act_dof_max=int(np.bincount(adof, minlength=max(nv, 1)).max()),
-              act_velfeedback=int(bool(((gt == 1) & (gp[:, 2] != 0.0)).any() or ((bt == 1) & (bp[:, 2] > 0.0)).any())))
+  feedback = ((gt == 1) & (gp[:, 2] != 0.0)) | ((bt == 1) & (bp[:, 2] != 0.0))
+  _check_trn_feedback(int((feedback & ~scalar).any()), int(mjm.opt.integrator))
+  facts = dict(act_dof_max=int(np.bincount(adof, minlength=max(nv, 1)).max()),
+               act_velfeedback=int(bool(((gt == 1) & (gp[:, 2] != 0.0)).any() or ((bt == 1) & (bp[:, 2] > 0.0)).any())),
+               trn_general=int(not scalar.all()), nJmom=int(nJmom), trn_feedback=int((feedback & ~scalar).any()))
+  return facts, dict(actuator_trntype=_arr(mjm.actuator_trntype, np.int32).reshape(nu), actuator_trnobj=trnid, actuator_trnjnt=trnjnt, **st)
 
 
 # Model arrays a host model may lack, and what stands in for them: a value fills the declared shape (a property the model's objects have by
@@ -598,7 +633,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   m.is_sparse = False
   m.nv_pad = _get_padded_sizes(nv, 1)[1]
   host = {"M_dense": _m_dense(mjm, nv)}  # ABI name -> numpy array in the declared dtype
-  for facts, arrays in (_tree_tables(mjm), _collision_facts(mjm, pairs, pairid), (_actuator_facts(mjm), {})):
+  for facts, arrays in (_tree_tables(mjm), _collision_facts(mjm, pairs, pairid), _actuator_facts(mjm)):
     for name, value in facts.items():
       setattr(m, name, value)
     host.update(arrays)
@@ -637,6 +672,8 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
     else:
       setattr(m, name, da)
   m.opt, m.stat = o, s
+  # (the joint ids behind MjhModel.actuator_trnid, see _actuator_facts; Model.actuator_trnid keeps the targets: the same array unless trn_general)
+  m.actuator_trnjnt = DeviceArray.from_numpy(host["actuator_trnjnt"]) if m.trn_general else m.actuator_trnid
   m.nxn_geom_pair_filtered = m.nxn_geom_pair
   m._ccd_flags_at_put = int(opt.disableflags)
   m.eq_active0 = _arr(getattr(mjm, "eq_active0", np.zeros(0)), np.int32)
@@ -702,11 +739,13 @@ def _c_heavy_colliders(m):
   return int(bool(m._heavy_pairs or bf_ != 3 or int(m.opt.broadphase) != 0 or m.sleep_enabled))
 
 
+# pointers of MjhModel that are not the Model attribute of the same name
+_C_MODEL_POINTERS = {"actuator_trnid": "actuator_trnjnt"}
 # scalars of MjhModel that are not plain Model attributes of the same name
 _C_MODEL_SCALARS = {
   **{name: (lambda m, name=name: int(getattr(m.opt, name)))
      for name in ("integrator", "cone", "solver", "iterations", "ls_iterations", "enableflags", "broadphase", "broadphase_filter", "ccd_iterations")},
-  "disableflags": _c_disableflags, "opt_sleep_tolerance": lambda m: float(m.opt_sleep_tolerance), "heavy_colliders": _c_heavy_colliders,
+  "integrator": lambda m: _check_trn_feedback(m.trn_feedback, int(m.opt.integrator)), "disableflags": _c_disableflags, "opt_sleep_tolerance": lambda m: float(m.opt_sleep_tolerance), "heavy_colliders": _c_heavy_colliders,
   "contact_sensor_maxmatch": lambda m: _check_maxmatch(m.opt.contact_sensor_maxmatch),
 }
 
@@ -718,7 +757,7 @@ def c_model(m: types.Model):
   c = _abi.CModel()
   for name, kind, ptr in _abi.MODEL_FIELDS:
     if ptr:
-      src = getattr(m.opt, name[4:]) if name.startswith("opt_") else getattr(m.stat, name[5:]) if name.startswith("stat_") else getattr(m, name)
+      src = getattr(m.opt, name[4:]) if name.startswith("opt_") else getattr(m.stat, name[5:]) if name.startswith("stat_") else getattr(m, _C_MODEL_POINTERS.get(name, name))
       setattr(c, name, src.ptr)
       if name in _BATCHED_MODEL_FIELDS:
         setattr(c, name + "_nb", src.shape[0])
@@ -771,7 +810,7 @@ def _needs_pgs_big(m: types.Model) -> bool:
 def _data_sizes(m: types.Model, nworld, nconmax, njmax, naconmax, handcap=None):
   """Every size the shapes of types.Data / Contact / Constraint name, for a Data of `m` with these capacities.  Workspaces of a kernel
   family the model does not run have a leading size of 0."""
-  sizes = {name: int(getattr(m, name)) for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nmocap", "neq", "nC", "ntree", "nsensordata", "nmaxpyramid")}
+  sizes = {name: int(getattr(m, name)) for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nmocap", "neq", "nC", "ntree", "nsensordata", "nmaxpyramid", "nJmom")}
   sizes["njmax_pad"], sizes["nv_pad"] = _get_padded_sizes(m.nv, njmax)
   concap, tree = contact_cap(nconmax), bool(m.tree_solve)
   sizes.update(
@@ -828,6 +867,9 @@ def _alloc_data(m: types.Model, nworld, nconmax, njmax, naconmax, mjd=None, nvma
   for name in ("nworld", "naconmax", "njmax", "njmax_pad", "nv_pad", "nsleepworld", "npgsworld", "nimpworld", "nccdworld", "nccdword", "concap"):
     setattr(d, name, sizes[name])
   d.nconmax = nconmax
+  # the structure of actuator_moment depends on the model only: the reference's per-world Data arrays are filled once, here
+  for name in ("moment_rownnz", "moment_rowadr", "moment_colind"):
+    setattr(d, name, DeviceArray.from_numpy(np.ascontiguousarray(np.tile(getattr(m, name).numpy().reshape(1, -1), (nworld, 1)))))
   d.ws_order.assign(np.arange(nworld, dtype=np.int32))
   d.sleep_pass = 0
   d.nvmax = int(nvmax)

@@ -1403,13 +1403,30 @@ def _compile(root, base_dir):
   gainmap = {"fixed": GAIN_FIXED, "affine": GAIN_AFFINE}
   biasmap = {"none": BIAS_NONE, "affine": BIAS_AFFINE}
   for i, a in enumerate(acts):
-    if "joint" not in a:
-      raise NotImplementedError("only joint transmissions are supported")
-    jid = m.jnt_names.index(a["joint"])
-    if m.jnt_type[jid] not in (JNT_HINGE, JNT_SLIDE):
-      raise NotImplementedError("actuators on ball/free joints")
-    m.actuator_trntype[i] = TRN_JOINT
-    m.actuator_trnid[i, 0] = jid
+    who = f"actuator {i} {a.get('name', '')!r}"
+    for key, what in (("body", "body (adhesion)"), ("cranksite", "slider-crank"), ("slidersite", "slider-crank"), ("tendon", "tendon")):
+      if key in a:
+        raise NotImplementedError(f"{who}: {what} transmissions are not built (joint, jointinparent and site transmissions are)")
+    targets = [key for key in ("joint", "jointinparent", "site") if key in a]
+    if len(targets) != 1:
+      raise ValueError(f"{who}: exactly one of joint / jointinparent / site must name the transmission target, got {targets or 'none'}")
+    if "refsite" in a and targets[0] != "site":
+      raise ValueError(f"{who}: refsite needs a site transmission")
+
+    def _index(names, key, kind):
+      if a[key] not in names:
+        raise ValueError(f"{who}: unknown {kind} {a[key]!r}")
+      return names.index(a[key])
+
+    if targets[0] == "site":
+      site_names = [s_["name"] for s_ in sites]
+      m.actuator_trntype[i] = TRN_SITE
+      m.actuator_trnid[i, 0] = _index(site_names, "site", "site")
+      if "refsite" in a:
+        m.actuator_trnid[i, 1] = _index(site_names, "refsite", "site")
+    else:
+      m.actuator_trntype[i] = TRN_JOINT if targets[0] == "joint" else TRN_JOINTINPARENT
+      m.actuator_trnid[i, 0] = _index(m.jnt_names, targets[0], "joint")
     for key, table_, dflt in (("dyntype", dynmap, "none"), ("gaintype", gainmap, "fixed"), ("biastype", biasmap, "none")):
       if a.get(key, dflt) not in table_:
         raise NotImplementedError(f"actuator {key} '{a[key]}'")
@@ -1959,11 +1976,13 @@ def set_const(m):
     elif ro < MJ_MINVAL and tr > MJ_MINVAL:
       ro = tr
     m.body_invweight0[b] = [tr, ro]
-  # actuator_acc0 = |M^-1 moment| for joint transmissions (set_const.py:494-506)
-  for i in range(m.nu):
-    mom = np.zeros(nv)
-    mom[m.jnt_dofadr[m.actuator_trnid[i, 0]]] = m.actuator_gear[i, 0]
-    m.actuator_acc0[i] = float(np.linalg.norm(Minv @ mom))
+  # actuator_acc0 = |M^-1 moment(qpos0)| from the dense moment row (set_const.py:494-506)
+  if m.nu:
+    from . import trn_tables as transmission
+
+    _, moment = transmission.host_moment(m, m.qpos0, h)
+    for i in range(m.nu):
+      m.actuator_acc0[i] = float(np.linalg.norm(Minv @ moment[i]))
   _sleep_tables(m, h)
 
 
@@ -1977,8 +1996,10 @@ def _sleep_tables(m, h):
   the body's equivalent-inertia-box half extent), which makes |dof_length * qvel| a linear speed as sleep_tolerance expects."""
   nv = m.nv
   m.tree_sleep_policy = np.full(m.ntree, 2, dtype=np.int32)  # SleepPolicy.AUTO_ALLOWED
-  for i in range(m.nu):
-    m.tree_sleep_policy[m.dof_treeid[m.jnt_dofadr[m.actuator_trnid[i, 0]]]] = 1  # SleepPolicy.AUTO_NEVER
+  if m.nu:  # (every tree that owns a column of some actuator's moment row)
+    from . import trn_tables as transmission
+
+    m.tree_sleep_policy[np.asarray(m.dof_treeid)[transmission.moment_structure(m)["moment_colind"]]] = 1  # SleepPolicy.AUTO_NEVER
   m.dof_length = np.ones(nv)
   if nv == 0:
     return

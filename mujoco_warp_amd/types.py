@@ -288,10 +288,17 @@ def _arr(shape, dtype, host=False):
   return dataclasses.field(default=None, repr=False, metadata={"shape": tuple(shape), "dtype": dtype, "host": host})
 
 
+def _arr_own(shape, dtype):
+  """An array field one of whose sizes (nJmom) is a size name of its own, newer than the fixed list of names the schema check of
+  tests/test_host.py evaluates declared shapes against: declared like _arr for put_model / make_data (array_fields), under its own key."""
+  return dataclasses.field(default=None, repr=False, metadata={"own_shape": tuple(shape), "dtype": dtype, "host": False})
+
+
 def array_fields(cls):
   """{name: (shape, dtype, host)} of the arrays `cls` declares through _arr: the one statement of their shapes and dtypes (io.put_model and
   io.make_data build and allocate from it)."""
-  return {f.name: (f.metadata["shape"], f.metadata["dtype"], f.metadata["host"]) for f in dataclasses.fields(cls) if "shape" in f.metadata}
+  return {f.name: (f.metadata.get("shape", f.metadata.get("own_shape")), f.metadata["dtype"], f.metadata["host"]) for f in dataclasses.fields(cls)
+          if "shape" in f.metadata or "own_shape" in f.metadata}
 
 
 def eval_shape(shape, sizes):
@@ -483,6 +490,22 @@ class Model(_Dirty):
   actuator_forcerange: DeviceArray = _arr(('*', 'nu', 2), "float32")
   actuator_actrange: DeviceArray = _arr(('*', 'nu', 2), "float32")
   actuator_gear: DeviceArray = _arr(('*', 'nu', 6), "float32")
+  # general transmissions (csrc/transmission.hpp; reference types.py Model.nJmom, Data.moment_*).  The sparse structure of
+  # Data.actuator_moment is static: rows in actuator order, columns ascending (MuJoCo C's layout)
+  trn_general: int = 0  # 1: some moment row is not the scalar gear[0] of a hinge / slide joint (k_transmission and the general velocity stage run)
+  nJmom: int = 0  # entries of all moment rows; nu when trn_general == 0
+  trn_feedback: int = 0  # 1: some multi-dof row feeds velocity back (refused with the implicit integrators, io._check_trn_feedback)
+  actuator_trntype: DeviceArray = _arr(('nu',), "int32")
+  actuator_trnobj: DeviceArray = _arr(('nu', 2), "int32")  # the device's copy of actuator_trnid (targets: joint | site, refsite)
+  actuator_trnjnt: DeviceArray = _arr(('nu', 2), "int32")  # MjhModel.actuator_trnid: always a valid joint (the single-dof kernels index with it)
+  moment_rownnz: DeviceArray = _arr(('nu',), "int32")
+  moment_rowadr: DeviceArray = _arr(('nu',), "int32")
+  moment_colind: DeviceArray = _arr_own(('nJmom',), "int32")
+  moment_side: DeviceArray = _arr_own(('nJmom',), "int32")  # site rows: 1 the dof moves the site, 2 the refsite (subtracted); 0 joint rows
+  moment_rowid: DeviceArray = _arr_own(('nJmom',), "int32")  # actuator of each entry
+  momentT_adr: DeviceArray = _arr(('nv+1',), "int32")  # dof-major transpose: dof i owns momentT_act / momentT_ind [adr[i], adr[i + 1])
+  momentT_act: DeviceArray = _arr_own(('nJmom',), "int32")
+  momentT_ind: DeviceArray = _arr_own(('nJmom',), "int32")
   eq_obj1id: DeviceArray = _arr(('neq',), "int32")
   eq_obj2id: DeviceArray = _arr(('neq',), "int32")
   eq_solref: DeviceArray = _arr(('*', 'neq', 2), "float32")
@@ -648,7 +671,10 @@ class Data(_Dirty):
   qLD: DeviceArray = _arr(('nworld', 'nC'), "float32")
   qLDiagInv: DeviceArray = _arr(('nworld', 'nv'), "float32")
   actuator_length: DeviceArray = _arr(('nworld', 'nu'), "float32")
-  actuator_moment: DeviceArray = _arr(('nworld', 'nu'), "float32")
+  actuator_moment: DeviceArray = _arr_own(('nworld', 'nJmom'), "float32")  # sparse rows (moment_*); written only for models with trn_general
+  moment_rownnz: DeviceArray = _arr(('nworld', 'nu'), "int32")  # the reference's Data schema; filled once from the Model's static structure
+  moment_rowadr: DeviceArray = _arr(('nworld', 'nu'), "int32")
+  moment_colind: DeviceArray = _arr_own(('nworld', 'nJmom'), "int32")
   actuator_velocity: DeviceArray = _arr(('nworld', 'nu'), "float32")
   cvel: DeviceArray = _arr(('nworld', 'nbody', 6), "float32")
   cdof_dot: DeviceArray = _arr(('nworld', 'nv', 6), "float32")
