@@ -257,6 +257,21 @@ typedef struct MjhModel {
   const float* eq_solref; int eq_solref_nb;
   const float* eq_solimp; int eq_solimp_nb;
   const float* eq_data; int eq_data_nb;
+  /* actuator / sensor delays (csrc/history.hpp; an addition within ABI v45 that is NOT at the tail: the contact sensors' block below stays
+     last, so only its four offsets move).  A buffer of Data.history is [user, cursor, times[nsample], values[nsample * dim]] at *_historyadr;
+     actuator buffers first, then sensor buffers, each in id order */
+  int nhistory;                 /* floats of one world's row of Data.history; 0: no kernel of csrc/history.hpp is ever launched                   */
+  int nu_history;               /* actuators with nsample > 0; > 0: forward / step / fwd_actuation read ctrl through k_history_ctrl               */
+  int nsensor_history_posvel;   /* sensors with nsample > 0 of the position / velocity stage launch (launch_sensor stage 0) ...                  */
+  int nsensor_history_acc;      /* ... and of the acceleration stage launch (stage 1): k_history_sensor follows that launch                     */
+  const int* actuator_history;  /* [nu, 2] nsample, interp (0 zero-order hold, 1 linear, 2 cubic)                                                */
+  const int* actuator_historyadr; /* [nu] first float of the actuator's buffer in a row of Data.history, -1: none                               */
+  const float* actuator_delay;  /* [nu] seconds                                                                                                  */
+  const int* sensor_history;    /* [nsensor, 2] nsample, interp                                                                                  */
+  const int* sensor_historyadr; /* [nsensor] */
+  const float* sensor_delay;    /* [nsensor] */
+  const int* sensor_history_posvel; /* [nsensor] ids of the stage-0 sensors with nsample > 0 first, -1 after them                              */
+  const int* sensor_history_acc;    /* [nsensor] the same for stage 1                                                                            */
   /* contact sensors (csrc/sensor_contact.hpp; an addition within ABI v45: appended, so that every earlier field keeps its offset) */
   int nsensor_contact;          /* sensors of type 42 (mjSENS_CONTACT); 0: the acceleration-stage sensor launch is not followed by k_sensor_contact */
   int contact_sensor_maxmatch;  /* Option.contact_sensor_maxmatch: matches kept per (world, sensor), 1..64 (one wavefront: lane k owns match k)   */
@@ -342,6 +357,9 @@ typedef struct MjhData {
   int* eq_active;      /* [nworld, neq] Data.eq_active (types.py:2262), initialised from eq_active0 */
   float* ws_rk;        /* [nworld, nq + 3 nv + 2 na] RK4 scratch: qpos, qvel, act at t0 and the weighted sums of qvel, qacc,
                           act_dot (the temporaries forward.rungekutta4 allocates per step, forward.py:530-540) */
+  /* actuator / sensor delays (csrc/history.hpp; an addition within ABI v45 in front of ws_contact, which stays the struct's last member) */
+  float* history;      /* [nworld, nhistory] the ring buffers of the delayed actuators and sensors (MjhModel.*_historyadr) */
+  float* ws_ctrl_delayed; /* [nworld, nu] what the actuation stage reads as ctrl in a model with nu_history > 0 (k_history_ctrl writes it) */
   float* ws_contact;   /* [nworld, concap, 32] per-world contact records (collision -> make_constraint hand-off;
                           the public contact_* arrays are compacted from these off the critical path) */
 } MjhData;
@@ -422,6 +440,19 @@ int mjh_camera_rays(const MjhModel* m, const MjhData* d, const MjhRender* rc, fl
 /* cli._ctrl_noise cli.py:103-145; ctrl_center may be NULL (-> actuator midpoint); worldid is global */
 int mjh_ctrl_noise(const MjhModel* m, const MjhData* d, const float* ctrl_center, int step, float noise_std,
                    float noise_rate, void* stream);
+
+/* Actuator / sensor history buffers (csrc/history.hpp; reference history.py read_ctrl / read_sensor / init_ctrl_history / init_sensor_history;
+ * additions within ABI v45).  is_sensor selects the sensor (1) or actuator (0) tables; id is the sensor / actuator.
+ * mjh_history_read: result[w, 0..dim) = the buffer of `id` read at time[w] - delay[id] (time: [nworld] device) with interpolation `interp`
+ * (-1: the model's, 0 zero-order hold, 1 linear, 2 cubic); result rows are result_stride floats apart.  An actuator / sensor without a buffer
+ * (nsample == 0) returns Data.ctrl / Data.sensordata.
+ * mjh_history_init: fills the buffer of `id` (nsample > 0) in every world with the samples values[w, 0 .. nsample * dim) (rows values_stride floats
+ * apart), oldest first, at the times times[0 .. nsample) (device; the caller checks that they increase strictly) or, when times is NULL, at
+ * -1e10; the cursor becomes nsample - 1; the user slot becomes phase[w], or keeps its value when phase is NULL. */
+int mjh_history_read(const MjhModel* m, const MjhData* d, int is_sensor, int id, const float* time, int interp, float* result, int result_stride,
+                     void* stream);
+int mjh_history_init(const MjhModel* m, const MjhData* d, int is_sensor, int id, const float* times, const float* values, int values_stride,
+                     const float* phase, void* stream);
 
 /* hipGraph capture/replay of one step (the reference captures step in a CUDA graph, cli.py:262-265) */
 int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** graph_exec_out);

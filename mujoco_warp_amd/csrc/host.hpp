@@ -12,6 +12,8 @@
 //   sensor_contact_tu.hip (k_sensor_contact: the contact sensors behind the acceleration-stage sensor launch),
 //   sensor_collision_tu.hip (k_sensor_collision: the geom distance sensors behind the position-stage sensor launch),
 //   transmission_tu.hip (k_transmission, k_fwd_vel_trn: general actuator transmissions, only for models with MjhModel.trn_general),
+//   history_tu.hip (k_history_ctrl, k_history_sensor, k_history_read, k_history_init and the entry points mjh_history_read / mjh_history_init:
+//   actuator and sensor delays, only for models with MjhModel.nhistory > 0),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
@@ -176,3 +178,7 @@ int launch_sensor_collision(const MjhModel* m, const MjhData* d, hipStream_t s);
 // stage, and the velocity stage's instantiation that reads the sparse moment rows (lanes64: the caller's lane choice for the model)
 int launch_transmission(const MjhModel* m, const MjhData* d, hipStream_t s);
 int launch_vel_trn(const MjhModel* m, const MjhData* d, int first, int last, bool lanes64, hipStream_t s);
+// actuator / sensor delays (history.hpp, history_tu.hip; MjhModel.nu_history / nsensor_history_*): Data.ws_ctrl_delayed from the actuators' buffers at
+// Data.time (insert: and ctrl into them), and behind the sensor launch of `stage` the delayed read / insert of that stage's sensors with a buffer
+int launch_history_ctrl(const MjhModel* m, const MjhData* d, int insert, hipStream_t s);
+int launch_history_sensor(const MjhModel* m, const MjhData* d, int stage, int insert, hipStream_t s);

@@ -246,7 +246,8 @@ static int launch_subtree_vel(const MjhModel* m, const MjhData* d, hipStream_t s
   hipLaunchKernelGGL(k_subtree_vel<32>, dim3((d->nworld + wpb - 1) / wpb), dim3(32 * wpb), lds, s, *m, *d);
   return MJH_OK;
 }
-static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStream_t s) {  // stage 1: acceleration-stage sensors (after the solver)
+// hist_insert: the sensors with a history buffer (csrc/history.hpp) store their fresh values -- every evaluation but the RK4 sub-evaluations
+static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert = true) {  // stage 1: acceleration-stage sensors (after the solver)
   if (stage == 0 && ((m->enableflags & ENBL_ENERGY) || m->nsensor_energy > 0)) {  // Data.energy rides with the position / velocity stage sensors (forward.py:1326-1338)
     if (!d->energy) return fail(MJH_E_ARG, "Data.energy missing (allocate Data with make_data/put_data)");
     hipLaunchKernelGGL(k_energy<32>, dim3((d->nworld + 7) / 8), dim3(256), 0, s, *m, *d);
@@ -265,6 +266,8 @@ static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStre
     hipLaunchKernelGGL(k_sensor, dim3((d->nworld * m->nsensor + 255) / 256), dim3(256), 0, s, *m, *d, stage);
   if (stage == 0 && m->nsensor_collision > 0) TRY(launch_sensor_collision(m, d, s));  // (k_sensor skips their slots)
   if (stage == 1 && m->nsensor_contact > 0) TRY(launch_sensor_contact(m, d, s));  // (k_sensor skips their slots)
+  // delayed sensors of this stage: sensordata = their buffer at time - delay, then the fresh values go into the buffer (no launch without them)
+  if ((stage == 0 ? m->nsensor_history_posvel : m->nsensor_history_acc) > 0) TRY(launch_history_sensor(m, d, stage, hist_insert ? 1 : 0, s));
   return MJH_OK;
 }
 static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s);  // = the solver workgroups of k_solve_plus
@@ -824,7 +827,9 @@ static int run_sleep_step(const MjhModel* m, const MjhData* d, bool step, hipStr
   return MJH_OK;
 }
 
-static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t s) {
+static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert = true);
+// hist_insert: see run_stage below
+static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert) {
   switch (stage) {
     case MJH_STAGE_KINEMATICS: { Scope sc(K_POS); return launch_pos(m, d, POS_KINEMATICS, POS_KINEMATICS, s); }
     case MJH_STAGE_COM_POS: { Scope sc(K_POS); return launch_pos(m, d, POS_COM, POS_COM, s); }
@@ -872,9 +877,9 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
       hipLaunchKernelGGL(k_energy<32>, dim3((d->nworld + 7) / 8), dim3(256), 0, s, *m, *d);
       return MJH_OK;
     }
-    case MJH_STAGE_SENSOR: { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s)); return launch_sensor(m, d, 1, s); }
-    case MJH_STAGE_SENSOR_POSVEL: { Scope sc(K_OTHER); return launch_sensor(m, d, 0, s); }
-    case MJH_STAGE_SENSOR_ACC: { Scope sc(K_OTHER); return launch_sensor(m, d, 1, s); }
+    case MJH_STAGE_SENSOR: { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); return launch_sensor(m, d, 1, s, hist_insert); }
+    case MJH_STAGE_SENSOR_POSVEL: { Scope sc(K_OTHER); return launch_sensor(m, d, 0, s, hist_insert); }
+    case MJH_STAGE_SENSOR_ACC: { Scope sc(K_OTHER); return launch_sensor(m, d, 1, s, hist_insert); }
     case MJH_STAGE_UPDATE_SLEEP:
     case MJH_STAGE_WAKE:
     case MJH_STAGE_WAKE_COLLISION:
@@ -894,7 +899,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
       if (!d->ws_rk) return fail(MJH_E_ARG, "Data.ws_rk missing (allocate Data with make_data/put_data)");
       static const float A[4] = {0.5f, 0.5f, 1.0f, 0.0f}, B[4] = {1.0f / 6.0f, 1.0f / 3.0f, 1.0f / 3.0f, 1.0f / 6.0f};
       for (int k = 0; k < 4; ++k) {
-        if (k) TRY(run_stage(m, d, MJH_STAGE_FORWARD, s));
+        if (k) TRY(run_stage(m, d, MJH_STAGE_FORWARD, s, false));  // (history buffers: never written by a sub-evaluation)
         Scope sc(K_INTEGRATE);
         hipLaunchKernelGGL(k_rk4<32>, dim3((d->nworld + 7) / 8), dim3(8 * 32), sizeof(float) * 8 * (m->nv + 1), s, *m, *d, k, A[k], B[k]);
       }
@@ -904,8 +909,8 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
     case MJH_STAGE_STEP: {
       if (m->sleep_enabled) return run_sleep_step(m, d, stage == MJH_STAGE_STEP, s);
       if (stage == MJH_STAGE_STEP && m->integrator == INT_RK4) {
-        TRY(run_stage(m, d, MJH_STAGE_FORWARD, s));
-        return run_stage(m, d, MJH_STAGE_RUNGEKUTTA4, s);
+        TRY(run_stage(m, d, MJH_STAGE_FORWARD, s, hist_insert));
+        return run_stage(m, d, MJH_STAGE_RUNGEKUTTA4, s, hist_insert);
       }
       const bool instrumented = g_instr && g_instr->on;
       const bool plain = KNOB_ONCE_FLAG("MJH_PLAIN");  // developer knob: one plain kernel per stage, serial
@@ -917,9 +922,9 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
         { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
         { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
-        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s)); }
+        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); }
         { Scope sc(K_SOLVE); TRY(launch_solve(m, d, s)); }
-        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s)); }
+        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s, hist_insert)); }
         if (stage == MJH_STAGE_STEP) { Scope sc(K_INTEGRATE); TRY(launch_integrate(m, d, mode, s)); }
         Scope sc(K_OTHER);
         TRY(launch_publish(m, d, s));
@@ -943,7 +948,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         Scope sc(K_MID);
         TRY(launch_mid(m, d, !sched_done, s));
       }
-      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s)); }  // (no launch without sensors; before the solver, whose epilogue may integrate the state)
+      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); }  // (no launch without sensors; before the solver, whose epilogue may integrate the state)
       if (side) {
         // (tried in round 3: forking the factor after k_fwd_pos, beside k_mid, with qacc_smooth as a separate solve after k_mid -- humanoid
         // Newton + 1.5 %, Panda - 5 %: the extra launch and the slower k_mid cost more than the shorter join wait saves)
@@ -956,7 +961,7 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
         HIPCHK(hipEventRecord(side->join, side->stream));
       }
       { Scope sc(K_SOLVE); TRY(launch_solve_any(m, d, p, s)); }
-      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s)); }
+      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s, hist_insert)); }
       { Scope sc(K_INTEGRATE); TRY(launch_integrate_plus(m, d, p.mode, stage == MJH_STAGE_STEP && !p.fuse_euler, p.riders == RIDE_INTEGRATOR, s)); }
       if (side) HIPCHK(hipStreamWaitEvent(s, side->join, 0));  // every fork rejoins the caller's stream
       return MJH_OK;
@@ -964,6 +969,41 @@ static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t
     default:
       return fail(MJH_E_ARG, "unknown stage");
   }
+}
+
+// Every stage goes through here.  A model with delayed actuators (MjhModel.nu_history, csrc/history.hpp) enters forward / step / fwd_actuation through
+// k_history_ctrl: Data.ws_ctrl_delayed = the actuators' buffers read at Data.time (ctrl itself where there is no delay), and everything downstream
+// gets a copy of MjhData whose ctrl points there (as run_sleep_step hands the solver its masked copies).  A step also stores (time, ctrl) in the
+// buffers, once, in that launch: behind the read of the same lane, at the step's own start time.  hist_insert = false (the RK4 sub-evaluations:
+// forward on the perturbed state) keeps every buffer read-only -- the sensors' too, see launch_sensor.
+static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert) {
+  if (m->nu_history <= 0) return run_stage_impl(m, d, stage, s, hist_insert);
+  if (m->sleep_enabled) return fail(MJH_E_UNSUPPORTED, "actuator delays with sleeping enabled (the wake-by-input test reads ctrl)");
+  if (stage == MJH_STAGE_EULER || stage == MJH_STAGE_IMPLICIT || stage == MJH_STAGE_RUNGEKUTTA4) {
+    // the integrator stages of a step taken stage by stage (step1 / step2, forward + rungekutta4): the step's ctrl sample goes in here, at its start time
+    { Scope sc(K_OTHER); TRY(launch_history_ctrl(m, d, hist_insert ? 1 : 0, s)); }
+    if (stage == MJH_STAGE_RUNGEKUTTA4) return run_stage_impl(m, d, stage, s, hist_insert);  // (its forwards come back here with Data.ctrl)
+    MjhData d2 = *d;  // (the implicit integrators differentiate the actuator force: at the delayed ctrl)
+    d2.ctrl = d->ws_ctrl_delayed;
+    return run_stage_impl(m, &d2, stage, s, hist_insert);
+  }
+  if (stage != MJH_STAGE_FORWARD && stage != MJH_STAGE_STEP && stage != MJH_STAGE_FWD_ACTUATION) return run_stage_impl(m, d, stage, s, hist_insert);
+  if (g_noise.n > 0) {  // (the benchmark loop's control noise rides with the position launch, behind this one: such a model takes it as a launch of its own)
+    const NoiseArgs noise = g_noise;
+    g_noise.n = 0;
+    Scope sc(K_NOISE);
+    hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
+  }
+  // (an RK4 sub-evaluation, hist_insert == false: k_rk4 keeps Data.time at the step's start through all four evaluations, so the delayed ctrl the
+  // first one read -- before the step's sample went in, which with a tight nsample evicted the sample read -- holds for the other three)
+  if (hist_insert || stage != MJH_STAGE_FORWARD) { Scope sc(K_OTHER); TRY(launch_history_ctrl(m, d, stage == MJH_STAGE_STEP && hist_insert ? 1 : 0, s)); }
+  MjhData d2 = *d;
+  d2.ctrl = d->ws_ctrl_delayed;
+  if (stage == MJH_STAGE_STEP && m->integrator == INT_RK4) {
+    TRY(run_stage_impl(m, &d2, MJH_STAGE_FORWARD, s, hist_insert));
+    return run_stage_impl(m, d, MJH_STAGE_RUNGEKUTTA4, s, hist_insert);  // (its forwards come back here with Data.ctrl)
+  }
+  return run_stage_impl(m, &d2, stage, s, hist_insert);
 }
 
 static int launch_solve_m(const MjhModel* m, const MjhData* d, float* x, const float* y, int mul, hipStream_t s) {

@@ -299,7 +299,7 @@ class StepGraph:
     side.wait_stream(torch.cuda.current_stream())
     # mjh_graph_create runs one real step before capturing (kernel attributes cannot be set during capture): keep the state,
     # constructing a graph must not advance the simulation (the reference's capture does not either)
-    names = ["qpos", "qvel", "act", "ctrl", "time", "qacc_warmstart", "qacc", "solver_niter", "overflow", "sensordata", "energy", "act_dot"]
+    names = ["qpos", "qvel", "act", "ctrl", "time", "qacc_warmstart", "qacc", "solver_niter", "overflow", "sensordata", "energy", "act_dot", "history"]
     # sleeping models: the warm-up step would advance the sleep counters / wake state / island tables by one step
     names += ["tree_asleep", "tree_awake", "body_awake", "body_awake_ind", "dof_awake_ind", "ntree_awake", "nbody_awake", "nv_awake", "tree_island", "nisland"]
     keep = {k: getattr(d, k).t.clone() for k in names if getattr(d, k, None) is not None and getattr(d, k).size}

@@ -24,6 +24,7 @@ from . import types
 from .device import DeviceArray
 
 from .mjcf import SENS as mjcf_SENS  # mjtSensor values of the supported sensors
+from .mjcf import history_buffers, history_layout, history_row
 
 _BATCHED_MODEL_FIELDS = [n[:-3] for n, k, p in _abi.MODEL_FIELDS if n.endswith("_nb")]
 _MODEL_PTR_FIELDS = [n for n, k, p in _abi.MODEL_FIELDS if p]
@@ -524,6 +525,51 @@ def _sensor_facts(sensor_type):
               nsensor_contact=count((42,)), nsensor_collision=count((39, 40, 41)))
 
 
+_SENSOR_ACC_TYPES = (0, 1, 4, 5, 22, 33, 34, 42)  # what the acceleration-stage launches write (csrc/sensor.hpp k_sensor stage 1, k_sensor_contact)
+
+
+def _history_facts(mjm, nu, sensor_type, sensor_dim, names=None):
+  """(facts, host arrays) of the actuator / sensor delays (csrc/history.hpp).  Every name is read from the host model with a default -- a model
+  without them has no history.  The buffer addresses are this engine's own layout (mjcf.history_layout: actuators, then sensors, in id order,
+  MuJoCo's); a host model that brings addresses must agree with it.  Per sensor stage the ids of the sensors with a buffer, in the order the
+  stage's launches of csrc/sensor.hpp serve them.  Refused: a sensor interval, a delay without samples."""
+  ns = len(sensor_type)
+
+  def get(name, shape, dtype):
+    src = getattr(mjm, name, None)
+    if src is None or shape[0] == 0:  # (no such table, or no actuators / sensors for it to describe)
+      return np.zeros(shape, dtype=dtype)
+    if np.asarray(src).size != int(np.prod(shape)):
+      raise ValueError(f"{name} has {np.asarray(src).size} entries, expected shape {shape}")
+    return np.ascontiguousarray(np.asarray(src).reshape(shape), dtype=dtype)
+
+  ah, sh = get("actuator_history", (nu, 2), np.int32), get("sensor_history", (ns, 2), np.int32)
+  ad, sd = get("actuator_delay", (nu,), np.float32), get("sensor_delay", (ns,), np.float32)
+  interval = get("sensor_interval", (ns, 2), np.float32)
+  for kind, hist, delay in (("actuator", ah, ad), ("sensor", sh, sd)):
+    for i in range(len(hist)):
+      who = f"{kind} {i}" + (f" {names[i]!r}" if kind == "sensor" and names is not None and len(names) > i and names[i] else "")
+      if kind == "sensor" and interval[i].any():
+        raise NotImplementedError(f"{who}: sensor_interval {interval[i].tolist()} (period / phase sampling of a sensor) is not implemented")
+      if hist[i, 0] < 0 or not 0 <= hist[i, 1] <= 2 or delay[i] < 0.0:
+        raise ValueError(f"{who}: history (nsample, interp) = {hist[i].tolist()}, delay = {float(delay[i])}: nsample and delay must not be negative, interp is 0, 1 or 2")
+      if delay[i] > 0.0 and hist[i, 0] < 1:
+        raise ValueError(f"{who}: delay = {float(delay[i])} needs a history buffer, nsample >= 1")
+  aadr, sadr, nhistory = history_layout(ah[:, 0], sh[:, 0], sensor_dim)
+  for name, mine, nsample in (("actuator_historyadr", aadr, ah[:, 0]), ("sensor_historyadr", sadr, sh[:, 0])):
+    theirs = getattr(mjm, name, None)
+    if theirs is not None and (np.asarray(theirs).reshape(-1)[nsample > 0] != mine[nsample > 0]).any():
+      raise ValueError(f"{name} {np.asarray(theirs).tolist()} is not the layout of Data.history (actuator buffers, then sensor buffers, in id order): {mine.tolist()}")
+  if getattr(mjm, "nhistory", None) is not None and int(mjm.nhistory) != nhistory:
+    raise ValueError(f"nhistory = {int(mjm.nhistory)} does not agree with the buffers of the model ({nhistory} floats)")
+  acc = np.isin(sensor_type, _SENSOR_ACC_TYPES)
+  lists = [np.flatnonzero((sh[:, 0] > 0) & sel).astype(np.int32) for sel in (~acc, acc)]
+  pad = lambda ids: np.concatenate([ids, np.full(ns - len(ids), -1, dtype=np.int32)])
+  facts = dict(nhistory=nhistory, nu_history=int((ah[:, 0] > 0).sum()), nsensor_history_posvel=len(lists[0]), nsensor_history_acc=len(lists[1]))
+  return facts, dict(actuator_history=ah, actuator_historyadr=aadr, actuator_delay=ad, sensor_history=sh, sensor_historyadr=sadr, sensor_delay=sd,
+                     sensor_interval=interval, sensor_history_posvel=pad(lists[0]), sensor_history_acc=pad(lists[1]))
+
+
 CONTACT_SENSOR_MAXMATCH_CAP = 64  # csrc/sensor_contact.hpp: one wavefront per world, lane k owns match k
 
 
@@ -641,6 +687,12 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   host.update(arrays)
   host.update(_body_geoms(mjm, m.nbody))
   sizes = {k: v for k, v in vars(m).items() if isinstance(v, int) and not k.startswith("_")}
+  for name in ("sensor_type", "sensor_dim"):
+    host[name] = _host_array(mjm, name, sizes)
+  facts, arrays = _history_facts(mjm, m.nu, host["sensor_type"], host["sensor_dim"], getattr(mjm, "sensor_names", None))
+  for name, value in facts.items():
+    setattr(m, name, value)
+  host.update(arrays)
   for name in _MODEL_PTR_FIELDS:
     if name not in host:
       host[name] = _host_array(mjm, name, sizes)
@@ -654,6 +706,8 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   m.opt_sleep_tolerance = float(getattr(opt, "sleep_tolerance", 1e-4))
   if m.sleep_enabled and (host["tree_sleep_policy"] > int(types.SleepPolicy.AUTO_ALLOWED)).any():
     raise NotImplementedError("sleep policies NEVER / ALLOWED / INIT are not implemented (reference types.py:308).")
+  if m.sleep_enabled and m.nhistory > 0:
+    raise NotImplementedError("actuator / sensor delays (nhistory > 0) with sleeping enabled are not implemented: the wake-by-input test reads ctrl")
 
   for name, n in (batch_sizes or {}).items():
     key = {"timestep": "opt_timestep", "tolerance": "opt_tolerance", "gravity": "opt_gravity",
@@ -675,6 +729,10 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   # (the joint ids behind MjhModel.actuator_trnid, see _actuator_facts; Model.actuator_trnid keeps the targets: the same array unless trn_general)
   m.actuator_trnjnt = DeviceArray.from_numpy(host["actuator_trnjnt"]) if m.trn_general else m.actuator_trnid
   m.nxn_geom_pair_filtered = m.nxn_geom_pair
+  m.sensor_interval = DeviceArray.from_numpy(host["sensor_interval"])
+  # (host copies of the buffer layout: make_data / reset_data write the buffers' initial state, the read / init functions check their arguments)
+  m._history_buffers = history_buffers(*(host[k] for k in ("actuator_history", "actuator_historyadr", "sensor_history", "sensor_historyadr", "sensor_dim")))
+  m._history_host = {k: host[k] for k in ("actuator_history", "sensor_history", "sensor_dim")}
   m._ccd_flags_at_put = int(opt.disableflags)
   m.eq_active0 = _arr(getattr(mjm, "eq_active0", np.zeros(0)), np.int32)
   for name, width in (("key_qpos", m.nq), ("key_qvel", nv), ("key_ctrl", m.nu), ("key_mpos", 3 * m.nmocap), ("key_mquat", 4 * m.nmocap), ("key_act", m.na)):
@@ -810,7 +868,7 @@ def _needs_pgs_big(m: types.Model) -> bool:
 def _data_sizes(m: types.Model, nworld, nconmax, njmax, naconmax, handcap=None):
   """Every size the shapes of types.Data / Contact / Constraint name, for a Data of `m` with these capacities.  Workspaces of a kernel
   family the model does not run have a leading size of 0."""
-  sizes = {name: int(getattr(m, name)) for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nmocap", "neq", "nC", "ntree", "nsensordata", "nmaxpyramid", "nJmom")}
+  sizes = {name: int(getattr(m, name)) for name in ("nq", "nv", "nu", "na", "nbody", "njnt", "ngeom", "nsite", "nmocap", "neq", "nC", "ntree", "nsensordata", "nmaxpyramid", "nJmom", "nhistory")}
   sizes["njmax_pad"], sizes["nv_pad"] = _get_padded_sizes(m.nv, njmax)
   concap, tree = contact_cap(nconmax), bool(m.tree_solve)
   sizes.update(
@@ -877,6 +935,7 @@ def _alloc_data(m: types.Model, nworld, nconmax, njmax, naconmax, mjd=None, nvma
   if m.neq:
     d.eq_active.assign(np.tile(m.eq_active0, (nworld, 1)))
   _reset_mocap(m, d, None)
+  _reset_history(m, d, None, 0.0)
   d.nmaxpyramid = m.nmaxpyramid
   d.world_offset = 0
   d.nccdhand = (handcap if handcap is not None else _ccd_handcap(nworld, _collide_ccap(int(m.npair), d.concap))) if d.nccdworld else 0
@@ -955,6 +1014,11 @@ def put_data(mjm, mjd, nworld: int = 1, nconmax: Optional[int] = None, nccdmax: 
     if dst.size:
       dst.assign(np.broadcast_to(src.reshape((1,) + dst.shape[1:]), dst.shape))
   d.time.fill_(float(mjd.time))
+  if m.nhistory:  # the host's buffers verbatim (a MuJoCo state drops in); a host data without them: the initial state at its time
+    if getattr(mjd, "history", None) is not None and np.asarray(mjd.history).size == m.nhistory:
+      d.history.assign(np.tile(np.asarray(mjd.history, dtype=np.float32).reshape(1, -1), (nworld, 1)))
+    else:
+      _reset_history(m, d, None, float(mjd.time))
   if m.ntree and getattr(mjd, "tree_asleep", None) is not None:  # reference io.py:2010-2012, 2138-2140: the host sleep state, tiled
     asleep = np.asarray(mjd.tree_asleep, dtype=np.int32).reshape(1, -1)
     d.tree_asleep.assign(np.tile(asleep, (nworld, 1)))
@@ -1018,6 +1082,7 @@ def get_data_into(result, mjm, d: types.Data, world_id: int = 0):
     setattr(result, name, getattr(d, name).numpy()[w].copy())
   result.sensordata = d.sensordata.numpy()[w].astype(np.float64)  # reference io.py: sensordata / energy
   result.energy = d.energy.numpy()[w].astype(np.float64)
+  result.history = d.history.numpy()[w].astype(np.float64)  # reference io.py: history
 
 
 def _state_fields(m, d, sig):
@@ -1025,7 +1090,7 @@ def _state_fields(m, d, sig):
   if sig < 0 or sig >= (1 << int(types.State.NSTATE)):
     raise ValueError(f"invalid state signature {sig} >= 2^mjNSTATE")
   S = types.State
-  fields = [(S.TIME, d.time, 1), (S.QPOS, d.qpos, m.nq), (S.QVEL, d.qvel, m.nv), (S.ACT, d.act, m.na), (S.WARMSTART, d.qacc_warmstart, m.nv),
+  fields = [(S.TIME, d.time, 1), (S.QPOS, d.qpos, m.nq), (S.QVEL, d.qvel, m.nv), (S.ACT, d.act, m.na), (S.HISTORY, d.history, m.nhistory), (S.WARMSTART, d.qacc_warmstart, m.nv),
             (S.CTRL, d.ctrl, m.nu), (S.QFRC_APPLIED, d.qfrc_applied, m.nv), (S.XFRC_APPLIED, d.xfrc_applied, 6 * m.nbody), (S.EQ_ACTIVE, d.eq_active, m.neq),
             (S.MOCAP_POS, d.mocap_pos, 3 * m.nmocap), (S.MOCAP_QUAT, d.mocap_quat, 4 * m.nmocap)]
   return [(arr, n) for bit, arr, n in fields if (sig & int(bit)) and n > 0]
@@ -1034,7 +1099,7 @@ def _state_fields(m, d, sig):
 def state_size(m: types.Model, sig: int) -> int:
   """Number of floats of the state components selected by sig (reference mj_stateSize)."""
   S = types.State
-  sizes = {S.TIME: 1, S.QPOS: m.nq, S.QVEL: m.nv, S.ACT: m.na, S.WARMSTART: m.nv, S.CTRL: m.nu, S.QFRC_APPLIED: m.nv, S.XFRC_APPLIED: 6 * m.nbody,
+  sizes = {S.TIME: 1, S.QPOS: m.nq, S.QVEL: m.nv, S.ACT: m.na, S.HISTORY: m.nhistory, S.WARMSTART: m.nv, S.CTRL: m.nu, S.QFRC_APPLIED: m.nv, S.XFRC_APPLIED: 6 * m.nbody,
            S.EQ_ACTIVE: m.neq, S.MOCAP_POS: 3 * m.nmocap, S.MOCAP_QUAT: 4 * m.nmocap}
   return int(sum(n for bit, n in sizes.items() if sig & int(bit)))
 
@@ -1144,6 +1209,20 @@ def _reset_sleep(m, d, mask):
     dst.assign(val)
 
 
+def _reset_history(m, d, mask, time):
+  """Data.history of the worlds in `mask` (None: all) in its initial state at `time` (mjcf.history_row; the timestep is the world's own)."""
+  if not m.nhistory:
+    return
+  h = m.opt.timestep.numpy().reshape(-1).astype(np.float64)
+  rows = np.stack([history_row(m._history_buffers, m.nhistory, float(time), hw) for hw in h]).astype(np.float32)
+  val = rows[np.arange(d.nworld) % len(h)]
+  if mask is not None:
+    cur = d.history.numpy().copy()
+    cur[mask] = val[mask]
+    val = cur
+  d.history.assign(val)
+
+
 def _reset_state(m, d, qpos, qvel, act, ctrl, time, mask):
   def put(dst, val):
     if dst.size == 0:
@@ -1168,6 +1247,7 @@ def _reset_state(m, d, qpos, qvel, act, ctrl, time, mask):
   put(d.time, np.full(d.time.shape, time, dtype=np.float32))
   _reset_mocap(m, d, mask)
   _reset_sleep(m, d, mask)
+  _reset_history(m, d, mask, time)
   if m.neq:
     put(d.eq_active, np.tile(m.eq_active0, (d.nworld, 1)))
   if mask is None:

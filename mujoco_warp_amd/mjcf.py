@@ -150,6 +150,10 @@ class MjData:
     # sleep state (MjData.tree_asleep): < 0 awake (a countdown towards sleep), >= 0 asleep = next tree of the sleep cycle; the
     # reference's `--init_asleep` sets tree_asleep[:] = arange(ntree) before put_data (cli.py:167-168): every tree asleep on its own
     self.tree_asleep = np.full(int(getattr(m, "ntree", 0)), -(1 + 10), dtype=np.int32)
+    # delay buffers of actuators and sensors in their initial state (history_row)
+    nhistory = int(getattr(m, "nhistory", 0))
+    buffers = history_buffers(m.actuator_history, m.actuator_historyadr, m.sensor_history, m.sensor_historyadr, m.sensor_dim) if nhistory else []
+    self.history = history_row(buffers, nhistory, 0.0, float(m.opt.timestep))
 
 
 def mj_resetDataKeyframe(m, d, key):
@@ -165,6 +169,56 @@ def mj_resetDataKeyframe(m, d, key):
   d.qacc_warmstart[:] = 0.0
   d.qfrc_applied[:] = 0.0
   d.xfrc_applied[:] = 0.0
+
+
+# ---- actuator / sensor delays (csrc/history.hpp) -------------------------------------------------
+HISTORY_INTERP = {"zoh": 0, "linear": 1, "cubic": 2}
+
+
+def _history_attrs(a, who):
+  """(nsample, interp, delay) of an actuator or sensor element with the attributes `a`; `interval` is refused by name."""
+  if "interval" in a:
+    raise NotImplementedError(f"{who}: interval (period / phase sampling of a sensor) is not implemented")
+  delay, nsample, interp = float(a.get("delay", 0.0)), int(a.get("nsample", 0)), a.get("interp", "zoh")
+  if interp not in HISTORY_INTERP:
+    raise ValueError(f"{who}: interp must be one of zoh, linear, cubic, got {interp!r}")
+  if delay < 0.0 or nsample < 0:
+    raise ValueError(f"{who}: delay and nsample must not be negative")
+  if delay > 0.0 and nsample < 1:
+    raise ValueError(f"{who}: delay = {delay} needs a history buffer, nsample >= 1")
+  return nsample, HISTORY_INTERP[interp], delay
+
+
+def history_layout(actuator_nsample, sensor_nsample, sensor_dim):
+  """(actuator_historyadr, sensor_historyadr, nhistory): every actuator or sensor with nsample > 0 owns one buffer [user, cursor, times[n],
+  values[n * dim]] of a world's row of Data.history -- actuator buffers first (dim 1), then sensor buffers, each in id order; -1: no buffer."""
+  adr, out = 0, []
+  for nsample, dim in ((np.asarray(actuator_nsample, dtype=np.int64), None), (np.asarray(sensor_nsample, dtype=np.int64), np.asarray(sensor_dim, dtype=np.int64))):
+    a = np.full(len(nsample), -1, dtype=np.int32)
+    for i, n in enumerate(nsample):
+      if n > 0:
+        a[i] = adr
+        adr += 2 + int(n) * (1 + (1 if dim is None else int(dim[i])))
+    out.append(a)
+  return out[0], out[1], int(adr)
+
+
+def history_buffers(actuator_history, actuator_historyadr, sensor_history, sensor_historyadr, sensor_dim):
+  """[(adr, nsample, dim)] of the buffers the history tables describe."""
+  ah, sh = np.asarray(actuator_history).reshape(-1, 2), np.asarray(sensor_history).reshape(-1, 2)
+  out = [(int(actuator_historyadr[i]), int(ah[i, 0]), 1) for i in range(len(ah)) if ah[i, 0] > 0]
+  return out + [(int(sensor_historyadr[i]), int(sh[i, 0]), int(sensor_dim[i])) for i in range(len(sh)) if sh[i, 0] > 0]
+
+
+def history_row(buffers, nhistory, time, timestep):
+  """One world's row of Data.history in its initial state at `time`: every buffer holds zeros at the times time - (n - k) timestep, k = 0 ..
+  n - 1 (the newest one step in the past), cursor n - 1, user slot 0 -- so that a delayed actuator or sensor gives 0 until its delay has
+  passed and the input of `delay` ago from then on."""
+  row = np.zeros(nhistory, dtype=np.float64)
+  for adr, n, _ in buffers:
+    row[adr + 1] = n - 1
+    row[adr + 2 : adr + 2 + n] = time - (n - np.arange(n)) * timestep
+  return row
 
 
 # ---- parsing helpers ---------------------------------------------------------------------------
@@ -1398,12 +1452,15 @@ def _compile(root, base_dir):
   m.actuator_cranklength = np.zeros(nu)
   m.actuator_acc0 = np.zeros(nu)
   m.actuator_lengthrange = np.zeros((nu, 2))
+  m.actuator_history = np.zeros((nu, 2), dtype=np.int32)  # nsample, interp
+  m.actuator_delay = np.zeros(nu)
   na = 0
   dynmap = {"none": DYN_NONE, "integrator": DYN_INTEGRATOR, "filter": DYN_FILTER, "filterexact": DYN_FILTEREXACT}
   gainmap = {"fixed": GAIN_FIXED, "affine": GAIN_AFFINE}
   biasmap = {"none": BIAS_NONE, "affine": BIAS_AFFINE}
   for i, a in enumerate(acts):
     who = f"actuator {i} {a.get('name', '')!r}"
+    m.actuator_history[i, 0], m.actuator_history[i, 1], m.actuator_delay[i] = _history_attrs(a, who)
     for key, what in (("body", "body (adhesion)"), ("cranksite", "slider-crank"), ("slidersite", "slider-crank"), ("tendon", "tendon")):
       if key in a:
         raise NotImplementedError(f"{who}: {what} transmissions are not built (joint, jointinparent and site transmissions are)")
@@ -1694,9 +1751,10 @@ def _compile_sensors(m, root, site_names):
   for sec in root.findall("sensor"):
     for e in sec:
       a = e.attrib
+      hist = _history_attrs(a, f"sensor {len(rows)} <{e.tag}> {a.get('name', '')!r}")
       if e.tag in SENS_UNSUPPORTED:
         rows.append(dict(type=SENS_UNSUPPORTED[e.tag][0], datatype=0, needstage=3, objtype=0, objid=-1, reftype=0, refid=-1, dim=SENS_UNSUPPORTED[e.tag][1], cutoff=0.0,
-                         name=a.get("name", "")))
+                         name=a.get("name", ""), hist=hist))
         continue
       if e.tag not in SENS:
         raise NotImplementedError(f"sensor <{e.tag}> is not implemented")
@@ -1728,7 +1786,7 @@ def _compile_sensors(m, root, site_names):
           refid = lookup[reftype].index(a["refname"])
       rows.append(dict(type=SENS[e.tag], datatype=1 if e.tag == "touch" else 3 if e.tag in ("ballquat", "framequat") else (2 if (e.tag.startswith("frame") and e.tag.endswith("axis")) or e.tag == "normal" else 0),
                        needstage=_SENS_STAGE.get(e.tag, 1), objtype=objtype, objid=objid, reftype=reftype, refid=refid, dim=dim,
-                       cutoff=float(a.get("cutoff", 0.0)), name=a.get("name", ""), intprm=intprm))
+                       cutoff=float(a.get("cutoff", 0.0)), name=a.get("name", ""), intprm=intprm, hist=hist))
   m.nsensor = len(rows)
   m.sensor_intprm = np.array([r.get("intprm", (0, 0, 0)) for r in rows], dtype=np.int32).reshape(len(rows), 3)
   for k in ("type", "datatype", "needstage", "objtype", "objid", "reftype", "refid", "dim"):
@@ -1737,6 +1795,11 @@ def _compile_sensors(m, root, site_names):
   m.sensor_adr = np.concatenate([[0], np.cumsum(m.sensor_dim)[:-1]]).astype(np.int32) if rows else np.zeros(0, dtype=np.int32)
   m.nsensordata = int(m.sensor_dim.sum()) if rows else 0
   m.sensor_names = [r["name"] for r in rows]
+  # delays (csrc/history.hpp): the buffers of actuators and sensors share Data.history
+  m.sensor_history = np.array([r["hist"][:2] for r in rows], dtype=np.int32).reshape(len(rows), 2)
+  m.sensor_delay = np.array([r["hist"][2] for r in rows], dtype=np.float64)
+  m.sensor_interval = np.zeros((len(rows), 2))
+  m.actuator_historyadr, m.sensor_historyadr, m.nhistory = history_layout(m.actuator_history[:, 0], m.sensor_history[:, 0], m.sensor_dim if rows else [])
 
 
 def mixed_contact_params(m, g1, g2):

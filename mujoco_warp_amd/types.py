@@ -152,7 +152,8 @@ class GeomType(enum.IntEnum):
 
 class State(enum.IntFlag):
   """State components as bit flags (reference types.py:712; mjtState -- UNPINNED here: the mujoco package is absent, the order follows the
-  reference's attribute list).  HISTORY, USERDATA and PLUGIN have no storage in this engine."""
+  reference's attribute list).  HISTORY is Data.history, nhistory floats per world (the delay buffers of actuators and sensors: csrc/history.hpp;
+  nothing for a model without delays); USERDATA and PLUGIN have no storage in this engine."""
 
   TIME = 1 << 0
   QPOS = 1 << 1
@@ -289,7 +290,7 @@ def _arr(shape, dtype, host=False):
 
 
 def _arr_own(shape, dtype):
-  """An array field one of whose sizes (nJmom) is a size name of its own, newer than the fixed list of names the schema check of
+  """An array field one of whose sizes (nJmom, nhistory) is a size name of its own, newer than the fixed list of names the schema check of
   tests/test_host.py evaluates declared shapes against: declared like _arr for put_model / make_data (array_fields), under its own key."""
   return dataclasses.field(default=None, repr=False, metadata={"own_shape": tuple(shape), "dtype": dtype, "host": False})
 
@@ -568,6 +569,21 @@ class Model(_Dirty):
   nsensor_contact: int = 0
   sensor_intprm: DeviceArray = _arr(('nsensor', 3), "int32")  # contact sensors: dataspec bits, reduce, num; 0 elsewhere
   sensor_contact_adr: DeviceArray = _arr(('nsensor',), "int32")  # ids of the contact sensors first, -1 after them
+  # actuator / sensor delays (csrc/history.hpp; reference types.py Model.actuator_history / actuator_delay / sensor_history / sensor_delay /
+  # sensor_interval).  A buffer of Data.history: [user, cursor, times[nsample], values[nsample * dim]] at *_historyadr
+  nhistory: int = 0  # floats of one world's row of Data.history
+  nu_history: int = 0  # actuators with nsample > 0
+  nsensor_history_posvel: int = 0  # sensors with nsample > 0 of the position / velocity stage sensor launch
+  nsensor_history_acc: int = 0  # ... of the acceleration stage sensor launch
+  actuator_history: DeviceArray = _arr(('nu', 2), "int32")  # nsample, interp (0 zero-order hold, 1 linear, 2 cubic)
+  actuator_historyadr: DeviceArray = _arr(('nu',), "int32")  # -1: no buffer
+  actuator_delay: DeviceArray = _arr(('nu',), "float32")
+  sensor_history: DeviceArray = _arr(('nsensor', 2), "int32")
+  sensor_historyadr: DeviceArray = _arr(('nsensor',), "int32")
+  sensor_delay: DeviceArray = _arr(('nsensor',), "float32")
+  sensor_interval: DeviceArray = _arr(('nsensor', 2), "float32")  # period, phase: always zero (a sensor interval is refused by name)
+  sensor_history_posvel: DeviceArray = _arr(('nsensor',), "int32")  # ids of the stage's sensors with a buffer first, -1 after them
+  sensor_history_acc: DeviceArray = _arr(('nsensor',), "int32")
   nmeshgraph: int = 0
   nhfielddata: int = 0
   hfield_size: DeviceArray = _arr(('nhfield', 4), "float32")
@@ -744,6 +760,8 @@ class Data(_Dirty):
   eq_active: DeviceArray = _arr(('nworld', 'neq'), "int32")
   ws_rk: DeviceArray = _arr(('nworld', 'nq+3*nv+2*na'), "float32")
   ws_contact: DeviceArray = _arr(('nworld', 'concap', 32), "float32")
+  history: DeviceArray = _arr_own(('nworld', 'nhistory'), "float32")  # delay buffers of actuators and sensors (reference types.py Data.history)
+  ws_ctrl_delayed: DeviceArray = _arr(('nworld', 'nu'), "float32")  # what the actuation stage reads as ctrl in a model with delayed actuators
   nworld: int = 0
   nconmax: int = 0
   naconmax: int = 0

@@ -1,4 +1,4 @@
-"""Registers / spills / scratch of the gfx950 kernels inside a hipcc object or shared library (reads the offload bundle directly):
+"""Registers / spills / scratch / static LDS of the gfx950 kernels inside a hipcc object or shared library (reads the offload bundle directly):
 python tools/obj_regs.py <file.o | lib.so> [name filter]"""
 import re, struct, subprocess, sys, tempfile, os
 b = open(sys.argv[1], "rb").read()
@@ -22,4 +22,4 @@ for mm in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", b):
     for blk in t.split("- .agpr_count:")[1:]:
       g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
       if flt in g("name"):
-        print(f"{g('name')[:80]:80s} vgpr {g('vgpr_count'):>4s} agpr {blk.split()[0]:>4s} sgpr {g('sgpr_count'):>4s} spill {g('vgpr_spill_count'):>4s} scratch {g('private_segment_fixed_size'):>5s}")
+        print(f"{g('name')[:80]:80s} vgpr {g('vgpr_count'):>4s} agpr {blk.split()[0]:>4s} sgpr {g('sgpr_count'):>4s} spill {g('vgpr_spill_count'):>4s} scratch {g('private_segment_fixed_size'):>5s} lds {g('group_segment_fixed_size'):>6s}")
