@@ -83,6 +83,55 @@ void mjh_knob_latch(const char* name) {
     if (rc_ != MJH_OK) return rc_; \
   } while (0)
 
+// ---- the call context: what one entry-point call hands down to every launch it makes ---------------------------------------------------
+// optional per-kernel event instrumentation used by mjh_timed_steps
+struct Instr {
+  std::vector<hipEvent_t> ev;  // pairs
+  std::vector<int> cls;
+  bool plain = false;  // one plain kernel per stage instead of the fused launches
+  hipError_t err = hipSuccess;  // first failing hipEvent* call of a Scope (reported by mjh_timed_steps)
+};
+// An entry point (mjh_stage, mjh_graph_create, mjh_timed_steps, mjh_ctrl_noise) makes one on its stack and passes it down by reference; nothing
+// per-call lives in a global.  Launchers that need only a stream take run.s.
+struct Run {
+  hipStream_t s;
+  // the sensors and actuators with a history buffer (csrc/history.hpp) store their fresh values -- every evaluation but the RK4 sub-evaluations
+  bool hist_insert = true;
+  Instr* instr = nullptr;  // per-kernel event pairs are on: one stream, no side launches, every Scope records
+  // The benchmark loop's control noise (mjh_timed_steps), pending until something applies it.  ONE rule: the fused position launch carries it
+  // (launch_pos_plus_g); where there is none, the driver launches it (apply_noise) in front of the first launch that reads ctrl.
+  NoiseArgs noise = {0, 0, 0.0f, 0.0f, nullptr, 0};
+  explicit Run(void* stream) : s((hipStream_t)stream) {}
+};
+struct Scope {
+  Instr* in;
+  hipStream_t s;
+  int cls;
+  hipEvent_t a, b;
+  void note(hipError_t e) {
+    if (e != hipSuccess && in->err == hipSuccess) in->err = e;
+  }
+  Scope(const Run& run, int c) : in(run.instr), s(run.s), cls(c), a(nullptr), b(nullptr) {
+    if (in) {
+      note(hipEventCreate(&a));
+      note(hipEventCreate(&b));
+      if (a && b) note(hipEventRecord(a, s));
+    }
+  }
+  ~Scope() {
+    if (in && a && b) {
+      note(hipEventRecord(b, s));
+      in->ev.push_back(a);
+      in->ev.push_back(b);
+      in->cls.push_back(cls);
+    } else {
+      if (a) hipEventDestroy(a);
+      if (b) hipEventDestroy(b);
+    }
+  }
+};
+enum { K_NOISE = 0, K_POS = 1, K_COLLISION = 2, K_CONSTRAINT = 3, K_VEL = 4, K_SOLVE = 5, K_INTEGRATE = 6, K_OTHER = 7, K_MID = 8 };
+
 // pick threads per block in {256,128,64} maximising resident worlds per CU for the given LDS needs
 int pick_block(size_t shared_bytes, size_t per_world_bytes, int G, size_t* lds_out, bool prefer_small_arg) {
   const int small_env = KNOB_ONCE_INT("MJH_SMALL_BLOCKS", -1);  // developer knob
@@ -246,12 +295,14 @@ static int launch_subtree_vel(const MjhModel* m, const MjhData* d, hipStream_t s
   hipLaunchKernelGGL(k_subtree_vel<32>, dim3((d->nworld + wpb - 1) / wpb), dim3(32 * wpb), lds, s, *m, *d);
   return MJH_OK;
 }
-// hist_insert: the sensors with a history buffer (csrc/history.hpp) store their fresh values -- every evaluation but the RK4 sub-evaluations
-static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert = true) {  // stage 1: acceleration-stage sensors (after the solver)
-  if (stage == 0 && ((m->enableflags & ENBL_ENERGY) || m->nsensor_energy > 0)) {  // Data.energy rides with the position / velocity stage sensors (forward.py:1326-1338)
-    if (!d->energy) return fail(MJH_E_ARG, "Data.energy missing (allocate Data with make_data/put_data)");
-    hipLaunchKernelGGL(k_energy<32>, dim3((d->nworld + 7) / 8), dim3(256), 0, s, *m, *d);
-  }
+static int launch_energy(const MjhModel* m, const MjhData* d, hipStream_t s) {
+  if (!d->energy) return fail(MJH_E_ARG, "Data.energy missing (allocate Data with make_data/put_data)");
+  hipLaunchKernelGGL(k_energy<32>, dim3((d->nworld + 7) / 8), dim3(256), 0, s, *m, *d);
+  return MJH_OK;
+}
+static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, const Run& run) {  // stage 1: acceleration-stage sensors (after the solver)
+  const hipStream_t s = run.s;
+  if (stage == 0 && ((m->enableflags & ENBL_ENERGY) || m->nsensor_energy > 0)) TRY(launch_energy(m, d, s));  // Data.energy rides with the position / velocity stage sensors (forward.py:1326-1338)
   if (m->nsensor == 0 || (m->disableflags & DSBL_SENSOR) || (stage == 1 && m->nsensor_acc == 0)) return MJH_OK;
   if (stage == 1 && m->nsensor_frc > 0) {
     if (!d->cfrc_ext) return fail(MJH_E_ARG, "Data.cfrc_ext missing");
@@ -267,10 +318,9 @@ static int launch_sensor(const MjhModel* m, const MjhData* d, int stage, hipStre
   if (stage == 0 && m->nsensor_collision > 0) TRY(launch_sensor_collision(m, d, s));  // (k_sensor skips their slots)
   if (stage == 1 && m->nsensor_contact > 0) TRY(launch_sensor_contact(m, d, s));  // (k_sensor skips their slots)
   // delayed sensors of this stage: sensordata = their buffer at time - delay, then the fresh values go into the buffer (no launch without them)
-  if ((stage == 0 ? m->nsensor_history_posvel : m->nsensor_history_acc) > 0) TRY(launch_history_sensor(m, d, stage, hist_insert ? 1 : 0, s));
+  if ((stage == 0 ? m->nsensor_history_posvel : m->nsensor_history_acc) > 0) TRY(launch_history_sensor(m, d, stage, run.hist_insert ? 1 : 0, s));
   return MJH_OK;
 }
-static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s);  // = the solver workgroups of k_solve_plus
 // the linear system of the fully implicit integrator (csrc/implicit.hpp): Data.ws_iacc = (M - h dF/dv)^-1 M qacc
 static int launch_implicit(const MjhModel* m, const MjhData* d, hipStream_t s) {
   const ImpLayout lay = imp_layout(m->nv, m->nbody, 32);
@@ -401,33 +451,48 @@ static int solve_supported(const MjhModel* m, const MjhData* d) {
     return fail(MJH_E_UNSUPPORTED, "njmax > 192 with the register / LDS resident PGS kernels is not supported (nv <= 64, pyramidal)");
   return MJH_OK;
 }
-// Auxiliary streams per host thread and device for the solver variants of the per-island dispatch (nv > 64): the rare island classes (one
-// stream each: round 6) and the generic solver touch islands / worlds the common-class launch skips, so they run beside it instead of
-// after it.  Released by mjh_release_thread_resources().
+// The ONE set of side streams per host thread and device, created on first use and released by mjh_release_thread_resources().  Two users,
+// never in the same step:
+//   the per-island dispatch (nv > 64; launch_solve_any): the rare island classes (one stream each: round 6) and the generic solver touch
+//     islands / worlds the common-class launch skips, so they run beside it instead of after it -- all MJH_NAUX streams;
+//   the Newton riders (plan_step: RIDE_SIDE): the public-output riders (contact publication, L'DL factor + qacc_smooth) cannot ride with the
+//     solver launch (its 256 VGPRs throttle them) and cost 55 us at the end of the integrator launch; they run beside the solver instead --
+//     stream 0 and join 0.  Two event hops (fork after k_mid, join after the integrator), neither on the solver's critical path.
+// Round 6: the riders' stream IS the first auxiliary stream of the per-island solver.  A stream of its own cost every later model of the
+// process its solver concurrency: once it existed -- any Newton model of at most 32 dofs stepped earlier -- the four class launches of
+// clutter_synth ran 25 % slower (1.43 -> 1.07 M env-steps/s, tools/interference_probe.py: the runtime multiplexes user streams onto a few
+// hardware queues, and streams that share one run in order).  MJH_NO_AUX (developer knob): the set is ONE stream, at the lowest priority, for
+// the riders alone.  (Retired experiment, LAB_NOTES.md R3: high / normal priority -- no difference, queue priority does not arbitrate CU
+// slots; the riders' workgroups only get slots as the solver's retire.)  Under instrumentation (one stream, one event pair per launch) nothing
+// is created or handed out.
 #define MJH_NAUX 4
 #define MJH_NAUX_EAGER 4  // (see launch_solve_any: eager launches pay for the forks while few islands are awake, and win afterwards)
-struct Aux {
+struct Streams {
+  int n;  // streams in the set: MJH_NAUX, or 1 under MJH_NO_AUX
   hipStream_t stream[MJH_NAUX];
   hipEvent_t fork, join[MJH_NAUX];
 };
-static thread_local Aux* g_aux_per_dev[16] = {nullptr};
-static thread_local bool g_serial_solver = false;  // set while per-kernel instrumentation is on (one stream, one event pair per launch)
-static Aux* aux_streams() {
-  if (KNOB_ONCE_FLAG("MJH_NO_AUX") || g_serial_solver) return nullptr;  // (developer knob)
+static thread_local Streams* g_streams_per_dev[16] = {nullptr};
+static Streams* side_streams(const Run& run) {
+  if (run.instr) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!g_aux_per_dev[dev]) {
-    Aux* a = new Aux();
+  if (!g_streams_per_dev[dev]) {
+    Streams* a = new Streams();
+    a->n = KNOB_ONCE_FLAG("MJH_NO_AUX") ? 1 : MJH_NAUX;
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
     bool ok = hipEventCreateWithFlags(&a->fork, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < MJH_NAUX && ok; ++k)
-      ok = hipStreamCreateWithFlags(&a->stream[k], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&a->join[k], hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; k < a->n && ok; ++k)
+      ok = (a->n == 1 ? hipStreamCreateWithPriority(&a->stream[k], hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&a->stream[k], hipStreamNonBlocking)) == hipSuccess &&
+           hipEventCreateWithFlags(&a->join[k], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
       delete a;  // (a partially created set leaks a handle or two: only on an already failing device)
       return nullptr;
     }
-    g_aux_per_dev[dev] = a;
+    g_streams_per_dev[dev] = a;
   }
-  return g_aux_per_dev[dev];
+  return g_streams_per_dev[dev];
 }
 // ---- the step plan: every decision of a step that more than one launch depends on, taken ONCE ---------------------------------------
 // plan_step is the one place that decides which solver kernel serves (m, d) and where the public-output riders (contact publication, L'DL
@@ -504,7 +569,7 @@ static StepPlan plan_step(const MjhModel* m, const MjhData* d, int stage, bool i
     const int inl_force = KNOB_ONCE_INT("MJH_NEWTON_RIDERS", -1);
     const bool inl = step && !instrumented && (inl_force >= 0 ? inl_force != 0 : m->nv <= 16) && plan_family(m, d, p.ell, 0) == FAM_NEWTON_MFMA;
     // Newton only: the riders cannot ride with the solver launch of larger models (its 256 VGPRs throttle them) and cost 55 us at the end of the
-    // integrator launch; they run on a low-priority side stream beside the solver instead (see side_stream)
+    // integrator launch; they run on a side stream beside the solver instead (see side_streams)
     // (nv <= 32 only: beside the 64-lane solver of larger models the riders cost more than they save, G1 -3 %)
     const bool side = p.newton && m->nv <= KNOB_ONCE_INT("MJH_SIDE_NV", 32) && !instrumented && !inl && side_ok && !KNOB_ONCE_FLAG("MJH_NO_SIDE");  // developer knobs
     p.riders = inl || (m->solver == SOL_CG && m->nv <= 64) ? RIDE_SOLVER : side ? RIDE_SIDE : RIDE_INTEGRATOR;
@@ -533,7 +598,8 @@ static StepPlan plan_step(const MjhModel* m, const MjhData* d, int stage, bool i
   return p;
 }
 // the launches of the plan's solver family (fe: the solver's epilogue integrates; with_factor: the riders are its trailing workgroups)
-static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan& p, hipStream_t s) {
+static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan& p, const Run& run) {
+  const hipStream_t s = run.s;
   const int fe = p.fuse_euler, all = 0x7fffffff;
   const bool with_factor = p.riders == RIDE_SOLVER;
   // njmax > 192: the register-resident kernels end at 192 rows (6 x 32 / 3 x 64 lanes); the (rare) worlds beyond go to the generic
@@ -549,7 +615,8 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan&
       // register-resident kernels, the others by the generic solver below
       hipLaunchKernelGGL(k_isl_clear, dim3(1), dim3(64), 0, s, *d);
       hipLaunchKernelGGL(k_tree_rows, dim3(d->nworld), dim3(64), sizeof(int) * (size_t)(2 * std::max(d->njmax, 1) + 2 * m->ntree), s, *m, *d);
-      Aux* aux = aux_streams();
+      Streams* aux = side_streams(run);
+      if (aux && aux->n < MJH_NAUX) aux = nullptr;  // (MJH_NO_AUX)
       // One stream per rare island class (round 6).  clutter_synth, 2048 worlds, steps 100-300 (tools/clutter_ab.py, bit-identical states, two
       // interleaved rounds): hipGraph replay -- the reference's own way to run a step, cli.py:262-290 -- none 1.27, one shared side stream 1.29,
       // one each 1.43 M env-steps/s; eager launches 1.28 / 1.28 / 1.40.  (Eager, steps 0-100 -- five trees awake, every class launch nearly
@@ -626,7 +693,7 @@ static int launch_solve_any(const MjhModel* m, const MjhData* d, const StepPlan&
   }
   return fail(MJH_E_ARG, "launch_solve_any: unknown solver family");
 }
-static int launch_solve(const MjhModel* m, const MjhData* d, hipStream_t s) { return launch_solve_any(m, d, plan_step(m, d, MJH_STAGE_SOLVE, false), s); }  // (the bare solve: no riders, no fused integrator)
+static int launch_solve(const MjhModel* m, const MjhData* d, const Run& run) { return launch_solve_any(m, d, plan_step(m, d, MJH_STAGE_SOLVE, run.instr != nullptr), run); }  // (the bare solve: no riders, no fused integrator)
 // name of the solver family of (m, d) in a fused step -- the plan, nothing launched
 static const char* solver_kernel_name(const MjhModel* m, const MjhData* d) { return kFamilyName[plan_step(m, d, MJH_STAGE_STEP, false).family]; }
 // integrator workgroups (integrate) and the riders -- contact publication, L'DL factor + qacc_smooth -- (with_factor)
@@ -647,14 +714,19 @@ static int launch_integrate_plus(const MjhModel* m, const MjhData* d, int mode, 
   hipLaunchKernelGGL(k_integrate_plus<G>, dim3(nint + npub + nfac), dim3(256), lds, s, *m, *d, mode, nint, npub);
   return MJH_OK;
 }
+// the pending control noise (Run::noise) as a launch of its own, under its own class; mjh_ctrl_noise is this launch
+static void apply_noise(const MjhModel* m, const MjhData* d, Run& run) {
+  const NoiseArgs noise = run.noise;
+  run.noise.n = 0;
+  if (noise.n == 0) return;
+  Scope sc(run, K_NOISE);
+  hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, run.s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
+}
 // *sched_done: whether the launch carried the schedule workgroup (it needs >= 128 threads to be quick; otherwise it
-// rides with k_mid, whose workgroups always have 256)
-// control noise queued by mjh_timed_steps for the next fused step: it rides with that step's first launch
-static thread_local NoiseArgs g_noise = {0, 0, 0.0f, 0.0f, nullptr, 0};
+// rides with k_mid, whose workgroups always have 256).  The pending control noise rides with the same launch, or goes in front of the plain one.
 template <int G>
-static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) {
-  NoiseArgs noise = g_noise;
-  g_noise.n = 0;
+static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, Run& run) {
+  const hipStream_t s = run.s;
   const PosLayout lay = pos_layout(m->nq, m->nv, m->nbody, m->njnt, m->nC, last >= POS_FACTOR);
   size_t lds;
   const int threads = pick_block(sizeof(int) * pos_shared_words(m->nv, m->nC, m->nbody, m->njnt, m->nbodylevel, m->ngeom, m->nsite), sizeof(float) * lay.total, G, &lds);
@@ -664,10 +736,12 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
   // costs this launch 2 us.  (Retired experiment, LAB_NOTES.md R5: always as k_mid's last workgroup -- 0.2902 / 0.2745 against 0.2914 / 0.2698 ms per step here.)
   *sched_done = threads >= 128;
   if (threads < 128) {
-    if (noise.n) hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
+    apply_noise(m, d, run);
     return launch_pos(m, d, first, last, s);
   }
   lds = std::max(lds, (size_t)2048);  // (the schedule workgroup: 512 ints)
+  NoiseArgs noise = run.noise;
+  run.noise.n = 0;
   noise.sched = *sched_done ? 1 : 0;
   HIPCHK(set_lds(k_fwd_pos_plus<G>, lds));
   const int wpb = threads / G, npos = (d->nworld + wpb - 1) / wpb, nnoise = (noise.n + threads - 1) / threads;
@@ -678,8 +752,7 @@ static int launch_pos_plus_g(const MjhModel* m, const MjhData* d, int first, int
 // Never launched, kept instantiated: it shares the 16-lane helper functions with k_mid<16>, and without this second caller the compiler inlines and
 // allocates registers differently in k_mid<16> (24217 -> 24165 instructions).  It goes in a change that measures the Panda step (LAB_NOTES.md R6.14).
 template __global__ void k_fwd_pos_plus<16>(MjhModel, MjhData, int, int, int, NoiseArgs);
-static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, hipStream_t s) { return lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, s) : launch_pos_plus_g<32>(m, d, first, last, sched_done, s); }  // (never 16 lanes: see lanes16)
-
+static int launch_pos_plus(const MjhModel* m, const MjhData* d, int first, int last, bool* sched_done, Run& run) { return lanes64(m) && m->nbody > 32 ? launch_pos_plus_g<64>(m, d, first, last, sched_done, run) : launch_pos_plus_g<32>(m, d, first, last, sched_done, run); }  // (never 16 lanes: see lanes16)
 
 static int check(const MjhModel* m, const MjhData* d) {
   if (!m || !d) return fail(MJH_E_ARG, "null model/data");
@@ -692,82 +765,6 @@ static int check(const MjhModel* m, const MjhData* d) {
   return MJH_OK;
 }
 
-// optional per-kernel event instrumentation used by mjh_timed_steps
-struct Instr {
-  std::vector<hipEvent_t> ev;  // pairs
-  std::vector<int> cls;
-  hipStream_t s;
-  bool on = false;
-  bool plain = false;  // one plain kernel per stage instead of the fused launches
-  hipError_t err = hipSuccess;  // first failing hipEvent* call of a Scope (reported by mjh_timed_steps)
-};
-static thread_local Instr* g_instr = nullptr;
-struct Scope {
-  int cls;
-  hipEvent_t a, b;
-  bool on;
-  static void note(hipError_t e) {
-    if (e != hipSuccess && g_instr && g_instr->err == hipSuccess) g_instr->err = e;
-  }
-  explicit Scope(int c) : cls(c), a(nullptr), b(nullptr), on(g_instr && g_instr->on) {
-    if (on) {
-      note(hipEventCreate(&a));
-      note(hipEventCreate(&b));
-      if (a && b) note(hipEventRecord(a, g_instr->s));
-      else on = false;
-    }
-  }
-  ~Scope() {
-    if (on) {
-      note(hipEventRecord(b, g_instr->s));
-      g_instr->ev.push_back(a);
-      g_instr->ev.push_back(b);
-      g_instr->cls.push_back(cls);
-    } else {
-      if (a) hipEventDestroy(a);
-      if (b) hipEventDestroy(b);
-    }
-  }
-};
-enum { K_NOISE = 0, K_POS = 1, K_COLLISION = 2, K_CONSTRAINT = 3, K_VEL = 4, K_SOLVE = 5, K_INTEGRATE = 6, K_OTHER = 7, K_MID = 8 };
-
-// Newton only (plan_step: RIDE_SIDE): the public-output riders (contact publication, L'DL factor + qacc_smooth) cannot ride with the solver
-// launch (its 256 VGPRs throttle them) and cost 55 us at the end of the integrator launch; they run on a low-priority
-// side stream beside the solver instead.  Two event hops (fork after k_mid, join after the integrator), neither on the
-// solver's critical path; created on first use per host thread and device, released by mjh_release_thread_resources().
-struct Side {
-  hipStream_t stream;
-  hipEvent_t fork, join;
-  bool owns_stream;
-};
-static thread_local Side* g_side_per_dev[16] = {nullptr};
-static Side* side_stream() {
-  Side** per_dev = g_side_per_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!per_dev[dev]) {
-    Side* sd = new Side();
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
-    // Round 6: the side stream IS the first auxiliary stream of the per-island solver (aux_streams; the two are never used by the same step).
-    // A stream of its own cost every later model of the process its solver concurrency: once it existed -- any Newton model of at most 32
-    // dofs stepped earlier -- the four class launches of clutter_synth ran 25 % slower (1.43 -> 1.07 M env-steps/s, tools/interference_probe.py:
-    // the runtime multiplexes user streams onto a few hardware queues, and streams that share one run in order).  Without auxiliary streams
-    // (MJH_NO_AUX, instrumentation): a stream of its own at the lowest priority.  (Retired experiment, LAB_NOTES.md R3: high / normal priority
-    // -- no difference, queue priority does not arbitrate CU slots; the riders' workgroups only get slots as the solver's retire.)
-    Aux* shared = aux_streams();
-    sd->owns_stream = shared == nullptr;
-    if (shared) sd->stream = shared->stream[0];
-    if ((sd->owns_stream && hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, least) != hipSuccess) ||
-        hipEventCreateWithFlags(&sd->fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sd->join, hipEventDisableTiming) != hipSuccess) {
-      delete sd;
-      return nullptr;
-    }
-    per_dev[dev] = sd;
-  }
-  return per_dev[dev];
-}
 // one wavefront per world (csrc/sleep.hpp k_sleep)
 static int launch_sleep(const MjhModel* m, const MjhData* d, int phase, hipStream_t s) {
   const size_t lds = sizeof(int) * sleep_lds(m->ntree, m->nbody, m->nv, d->njmax, d->concap).total;
@@ -776,110 +773,131 @@ static int launch_sleep(const MjhModel* m, const MjhData* d, int phase, hipStrea
   hipLaunchKernelGGL(k_sleep, dim3(d->nworld), dim3(64), lds, s, *m, *d, phase);
   return MJH_OK;
 }
-// forward / step of a model with sleeping enabled (forward.py:345-349, 652-675, 1290-1324, 1341-1347): the staged launch sequence
-// with the sleep bookkeeping between the stages (csrc/sleep.hpp)
-static int run_sleep_step(const MjhModel* m, const MjhData* d, bool step, hipStream_t s) {
-  if (!d->tree_asleep || !d->ws_sleep_J) return fail(MJH_E_ARG, "Data sleep tables missing (allocate Data with make_data/put_data)");
-  if (m->solver != SOL_NEWTON) return fail(MJH_E_UNSUPPORTED, "sleeping requires the Newton solver (reference io.py:359)");
-  if (step && m->integrator == INT_RK4) return fail(MJH_E_UNSUPPORTED, "sleeping with the RK4 integrator");
-  const int mode = integrator_mode(m);
-  { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE, s)); }
-  { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); TRY(launch_trn(m, d, s)); }
-  { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
-  { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE_COLLISION, s)); }
-  {
+
+// ---- the unfused stage order: one plain kernel per stage, written ONCE ----------------------------------------------------------------
+// run_unfused is the whole forward / step; its pieces also serve MJH_STAGE_FWD_POSITION and the fused step of a trn_general model.  sleep: with
+// the sleep bookkeeping between the stages (csrc/sleep.hpp).
+static int launch_schedule(const MjhModel* m, const MjhData* d, const Run& run) {
+  Scope sc(run, K_OTHER);
+  hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, run.s, *d, sched_cls_host(*m, *d));
+  return MJH_OK;
+}
+// the position stage up to `last` and, behind it, the general transmissions
+static int run_pos_trn(const MjhModel* m, const MjhData* d, int last, const Run& run) {
+  Scope sc(run, K_POS);
+  TRY(launch_pos(m, d, POS_KINEMATICS, last, run.s));
+  return launch_trn(m, d, run.s);
+}
+static int run_collide_constrain(const MjhModel* m, const MjhData* d, bool sleep, const Run& run) {
+  const hipStream_t s = run.s;
+  { Scope sc(run, K_COLLISION); TRY(launch_collision(m, d, s)); }
+  if (sleep) {
+    { Scope sc(run, K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE_COLLISION, s)); }
     // pass 2: waking only ever lets more pairs through the sleep filter, so the pairs of pass 1 plus "the pairs pass 1 skipped that
     // involve a newly awakened body" are the pairs that pass the filter now: the woken worlds recompute their list
-    Scope sc(K_COLLISION);
+    Scope sc(run, K_COLLISION);
     MjhData d2 = *d;
     d2.sleep_pass = 2;
     TRY(launch_collision(m, &d2, s));
   }
-  { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
-  { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_POST_CONSTRAINT, s)); }
-  { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
-  { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s)); }
-  {
-    Scope sc(K_OTHER);
+  { Scope sc(run, K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
+  if (sleep) { Scope sc(run, K_OTHER); TRY(launch_sleep(m, d, (int)SLP_POST_CONSTRAINT, s)); }
+  return MJH_OK;
+}
+// collision -> constraint -> velocity: what k_mid does in one launch
+static int run_mid_unfused(const MjhModel* m, const MjhData* d, bool sleep, const Run& run) {
+  TRY(run_collide_constrain(m, d, sleep, run));
+  Scope sc(run, K_VEL);
+  return launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, run.s);
+}
+// forward / step as plain kernels: the profiling pass (so that the event pairs time one kernel at a time), MJH_PLAIN, and every model with
+// sleeping enabled (forward.py:345-349, 652-675, 1290-1324, 1341-1347)
+static int run_unfused(const MjhModel* m, const MjhData* d, bool step, bool sleep, Run& run) {
+  const hipStream_t s = run.s;
+  if (sleep) {
+    if (!d->tree_asleep || !d->ws_sleep_J) return fail(MJH_E_ARG, "Data sleep tables missing (allocate Data with make_data/put_data)");
+    if (m->solver != SOL_NEWTON) return fail(MJH_E_UNSUPPORTED, "sleeping requires the Newton solver (reference io.py:359)");
+    if (step && m->integrator == INT_RK4) return fail(MJH_E_UNSUPPORTED, "sleeping with the RK4 integrator");
+  }
+  apply_noise(m, d, run);  // (no fused position launch to carry it; the wake-by-input test of k_sleep reads ctrl)
+  if (sleep) { Scope sc(run, K_OTHER); TRY(launch_sleep(m, d, (int)SLP_WAKE, s)); }
+  else TRY(launch_schedule(m, d, run));
+  TRY(run_pos_trn(m, d, POS_CRB, run));
+  TRY(run_mid_unfused(m, d, sleep, run));
+  { Scope sc(run, K_OTHER); TRY(launch_sensor(m, d, 0, run)); }
+  MjhData masked;  // sleep: the solver reads the masked copies (sleeping dofs frozen), and writes the public outputs
+  if (sleep) {
+    Scope sc(run, K_OTHER);
     if (m->nv > 0) hipLaunchKernelGGL(k_sleep_qfrc, dim3((d->nworld * m->nv + 255) / 256), dim3(256), 0, s, *m, *d);
     hipLaunchKernelGGL(k_sleep_mask, dim3(d->nworld), dim3(256), 0, s, *m, *d);
+    masked = *d;
+    masked.efc_J = d->ws_sleep_J;
+    masked.qacc_warmstart = d->ws_sleep_warm;
   }
+  { Scope sc(run, K_SOLVE); TRY(launch_solve(m, sleep ? &masked : d, run)); }
+  { Scope sc(run, K_OTHER); TRY(launch_sensor(m, d, 1, run)); }
+  if (step) { Scope sc(run, K_INTEGRATE); TRY(launch_integrate(m, d, integrator_mode(m), s)); }
   {
-    Scope sc(K_SOLVE);
-    MjhData d3 = *d;  // the solver reads the masked copies (sleeping dofs frozen), and writes the public outputs
-    d3.efc_J = d->ws_sleep_J;
-    d3.qacc_warmstart = d->ws_sleep_warm;
-    TRY(launch_solve(m, &d3, s));
-  }
-  { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s)); }
-  if (step) { Scope sc(K_INTEGRATE); TRY(launch_integrate(m, d, mode, s)); }
-  {
-    // (round 6: these two public-output launches beside the solver on the side stream LOSE here -- clutter_synth 1.53 -> 1.36 M env-steps/s, two
-    // interleaved pairs: their workgroups take LDS slots from the island solves, which are the step's critical path)
-    Scope sc(K_OTHER);
+    // (round 6: these two public-output launches beside the solver on the side stream LOSE with sleeping -- clutter_synth 1.53 -> 1.36 M env-steps/s,
+    // two interleaved pairs: their workgroups take LDS slots from the island solves, which are the step's critical path)
+    Scope sc(run, K_OTHER);
     TRY(launch_publish(m, d, s));
-    TRY(launch_factor_smooth(m, d, 1, s));
+    TRY(launch_factor_smooth(m, d, m->solver == SOL_NEWTON ? 1 : 0, s));  // CG and PGS write qacc_smooth themselves
   }
-  if (step) {
-    { Scope sc(K_OTHER); TRY(launch_sleep(m, d, (int)SLP_SLEEP, s)); }
-    { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_RNE, s)); }
+  if (sleep && step) {
+    { Scope sc(run, K_OTHER); TRY(launch_sleep(m, d, (int)SLP_SLEEP, s)); }
+    { Scope sc(run, K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_RNE, s)); }
   }
   return MJH_OK;
 }
 
-static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert = true);
-// hist_insert: see run_stage below
-static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert) {
+static int run_stage(const MjhModel* m, const MjhData* d, int stage, Run& run);
+// one stage as its launches; STEP with the RK4 integrator never comes here (run_stage splits it)
+static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, Run& run) {
+  const hipStream_t s = run.s;
   switch (stage) {
-    case MJH_STAGE_KINEMATICS: { Scope sc(K_POS); return launch_pos(m, d, POS_KINEMATICS, POS_KINEMATICS, s); }
-    case MJH_STAGE_COM_POS: { Scope sc(K_POS); return launch_pos(m, d, POS_COM, POS_COM, s); }
-    case MJH_STAGE_CRB: { Scope sc(K_POS); return launch_pos(m, d, POS_CRB, POS_CRB, s); }
-    case MJH_STAGE_FACTOR_M: { Scope sc(K_POS); return launch_pos(m, d, POS_FACTOR, POS_FACTOR, s); }
+    case MJH_STAGE_KINEMATICS: { Scope sc(run, K_POS); return launch_pos(m, d, POS_KINEMATICS, POS_KINEMATICS, s); }
+    case MJH_STAGE_COM_POS: { Scope sc(run, K_POS); return launch_pos(m, d, POS_COM, POS_COM, s); }
+    case MJH_STAGE_CRB: { Scope sc(run, K_POS); return launch_pos(m, d, POS_CRB, POS_CRB, s); }
+    case MJH_STAGE_FACTOR_M: { Scope sc(run, K_POS); return launch_pos(m, d, POS_FACTOR, POS_FACTOR, s); }
     case MJH_STAGE_COLLISION:
-      { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
-      { Scope sc(K_OTHER); return launch_publish(m, d, s); }
+      { Scope sc(run, K_COLLISION); TRY(launch_collision(m, d, s)); }
+      { Scope sc(run, K_OTHER); return launch_publish(m, d, s); }
     case MJH_STAGE_MAKE_CONSTRAINT:
-      { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
-      { Scope sc(K_OTHER); return launch_publish(m, d, s); }
-    case MJH_STAGE_TRANSMISSION: { Scope sc(K_POS); return launch_trn(m, d, s); }  // (hinge / slide scalar rows only: the length is produced by fwd_actuation)
-    case MJH_STAGE_COM_VEL: { Scope sc(K_VEL); return launch_vel(m, d, VEL_COMVEL, VEL_COMVEL, s); }
-    case MJH_STAGE_PASSIVE: { Scope sc(K_VEL); return launch_vel(m, d, VEL_PASSIVE, VEL_PASSIVE, s); }
-    case MJH_STAGE_RNE: { Scope sc(K_VEL); return launch_vel(m, d, VEL_RNE, VEL_RNE, s); }
-    case MJH_STAGE_FWD_VELOCITY: { Scope sc(K_VEL); return launch_vel(m, d, VEL_COMVEL, VEL_RNE, s); }
-    case MJH_STAGE_FWD_ACTUATION: { Scope sc(K_VEL); return launch_vel(m, d, VEL_ACTUATION, VEL_ACTUATION, s); }
+      { Scope sc(run, K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
+      { Scope sc(run, K_OTHER); return launch_publish(m, d, s); }
+    case MJH_STAGE_TRANSMISSION: { Scope sc(run, K_POS); return launch_trn(m, d, s); }  // (hinge / slide scalar rows only: the length is produced by fwd_actuation)
+    case MJH_STAGE_COM_VEL: { Scope sc(run, K_VEL); return launch_vel(m, d, VEL_COMVEL, VEL_COMVEL, s); }
+    case MJH_STAGE_PASSIVE: { Scope sc(run, K_VEL); return launch_vel(m, d, VEL_PASSIVE, VEL_PASSIVE, s); }
+    case MJH_STAGE_RNE: { Scope sc(run, K_VEL); return launch_vel(m, d, VEL_RNE, VEL_RNE, s); }
+    case MJH_STAGE_FWD_VELOCITY: { Scope sc(run, K_VEL); return launch_vel(m, d, VEL_COMVEL, VEL_RNE, s); }
+    case MJH_STAGE_FWD_ACTUATION: { Scope sc(run, K_VEL); return launch_vel(m, d, VEL_ACTUATION, VEL_ACTUATION, s); }
     case MJH_STAGE_FWD_ACCELERATION:
-      { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_ACCEL, VEL_ACCEL, s)); }
-      { Scope sc(K_OTHER); return launch_factor_smooth(m, d, 1, s); }
-    case MJH_STAGE_SOLVE: { Scope sc(K_SOLVE); return launch_solve(m, d, s); }
-    case MJH_STAGE_EULER: { Scope sc(K_INTEGRATE); return launch_integrate(m, d, 0, s); }
-    case MJH_STAGE_IMPLICIT: { Scope sc(K_INTEGRATE); return launch_integrate(m, d, m->integrator == INT_IMPLICIT ? 2 : 1, s); }
-    case MJH_STAGE_FWD_POSITION:
-      { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_FACTOR, s)); TRY(launch_trn(m, d, s)); }
-      { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
-      { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
-      { Scope sc(K_OTHER); TRY(launch_publish(m, d, s)); }
-      return MJH_OK;
+      { Scope sc(run, K_VEL); TRY(launch_vel(m, d, VEL_ACCEL, VEL_ACCEL, s)); }
+      { Scope sc(run, K_OTHER); return launch_factor_smooth(m, d, 1, s); }
+    case MJH_STAGE_SOLVE: { Scope sc(run, K_SOLVE); return launch_solve(m, d, run); }
+    case MJH_STAGE_EULER: { Scope sc(run, K_INTEGRATE); return launch_integrate(m, d, 0, s); }
+    case MJH_STAGE_IMPLICIT: { Scope sc(run, K_INTEGRATE); return launch_integrate(m, d, m->integrator == INT_IMPLICIT ? 2 : 1, s); }
+    case MJH_STAGE_FWD_POSITION: {
+      TRY(run_pos_trn(m, d, POS_FACTOR, run));
+      TRY(run_collide_constrain(m, d, false, run));
+      Scope sc(run, K_OTHER);
+      return launch_publish(m, d, s);
+    }
     case MJH_STAGE_RNE_POSTCONSTRAINT: {
       if (!d->cfrc_ext) return fail(MJH_E_ARG, "Data.cfrc_ext missing");
-      Scope sc(K_OTHER);
-      TRY(launch_rne_postconstraint(m, d, s));
-      return MJH_OK;
+      Scope sc(run, K_OTHER);
+      return launch_rne_postconstraint(m, d, s);
     }
     case MJH_STAGE_SUBTREE_VEL: {
       if (!d->subtree_linvel || !d->subtree_angmom) return fail(MJH_E_ARG, "Data.subtree_linvel / subtree_angmom missing");
-      Scope sc(K_OTHER);
-      TRY(launch_subtree_vel(m, d, s));
-      return MJH_OK;
+      Scope sc(run, K_OTHER);
+      return launch_subtree_vel(m, d, s);
     }
-    case MJH_STAGE_ENERGY: {
-      if (!d->energy) return fail(MJH_E_ARG, "Data.energy missing (allocate Data with make_data/put_data)");
-      Scope sc(K_OTHER);
-      hipLaunchKernelGGL(k_energy<32>, dim3((d->nworld + 7) / 8), dim3(256), 0, s, *m, *d);
-      return MJH_OK;
-    }
-    case MJH_STAGE_SENSOR: { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); return launch_sensor(m, d, 1, s, hist_insert); }
-    case MJH_STAGE_SENSOR_POSVEL: { Scope sc(K_OTHER); return launch_sensor(m, d, 0, s, hist_insert); }
-    case MJH_STAGE_SENSOR_ACC: { Scope sc(K_OTHER); return launch_sensor(m, d, 1, s, hist_insert); }
+    case MJH_STAGE_ENERGY: { Scope sc(run, K_OTHER); return launch_energy(m, d, s); }
+    case MJH_STAGE_SENSOR: { Scope sc(run, K_OTHER); TRY(launch_sensor(m, d, 0, run)); return launch_sensor(m, d, 1, run); }
+    case MJH_STAGE_SENSOR_POSVEL: { Scope sc(run, K_OTHER); return launch_sensor(m, d, 0, run); }
+    case MJH_STAGE_SENSOR_ACC: { Scope sc(run, K_OTHER); return launch_sensor(m, d, 1, run); }
     case MJH_STAGE_UPDATE_SLEEP:
     case MJH_STAGE_WAKE:
     case MJH_STAGE_WAKE_COLLISION:
@@ -889,81 +907,59 @@ static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, hipStr
       if (!d->tree_asleep) return fail(MJH_E_ARG, "Data sleep tables missing (allocate Data with make_data/put_data)");
       const int phase = stage == MJH_STAGE_UPDATE_SLEEP ? SLP_UPDATE : stage == MJH_STAGE_WAKE ? SLP_WAKE : stage == MJH_STAGE_WAKE_COLLISION ? SLP_WAKE_COLLISION
                         : stage == MJH_STAGE_WAKE_EQUALITY ? SLP_WAKE_EQUALITY : stage == MJH_STAGE_ISLAND ? SLP_ISLAND : SLP_SLEEP;
-      Scope sc(K_OTHER);
-      TRY(launch_sleep(m, d, phase, s));
-      return MJH_OK;
+      Scope sc(run, K_OTHER);
+      return launch_sleep(m, d, phase, s);
     }
     case MJH_STAGE_RUNGEKUTTA4: {
       // forward.rungekutta4 (forward.py:524-557), called after a forward at t0: one k_rk4 launch after each evaluation
       // (accumulate + perturb; the last one restores t0 and advances); tableau A = (1/2, 1/2, 1), B = (1/6, 1/3, 1/3, 1/6)
       if (!d->ws_rk) return fail(MJH_E_ARG, "Data.ws_rk missing (allocate Data with make_data/put_data)");
       static const float A[4] = {0.5f, 0.5f, 1.0f, 0.0f}, B[4] = {1.0f / 6.0f, 1.0f / 3.0f, 1.0f / 3.0f, 1.0f / 6.0f};
+      Run sub = run;
+      sub.hist_insert = false;  // (history buffers: never written by a sub-evaluation)
       for (int k = 0; k < 4; ++k) {
-        if (k) TRY(run_stage(m, d, MJH_STAGE_FORWARD, s, false));  // (history buffers: never written by a sub-evaluation)
-        Scope sc(K_INTEGRATE);
+        if (k) TRY(run_stage(m, d, MJH_STAGE_FORWARD, sub));
+        Scope sc(run, K_INTEGRATE);
         hipLaunchKernelGGL(k_rk4<32>, dim3((d->nworld + 7) / 8), dim3(8 * 32), sizeof(float) * 8 * (m->nv + 1), s, *m, *d, k, A[k], B[k]);
       }
       return MJH_OK;
     }
     case MJH_STAGE_FORWARD:
     case MJH_STAGE_STEP: {
-      if (m->sleep_enabled) return run_sleep_step(m, d, stage == MJH_STAGE_STEP, s);
-      if (stage == MJH_STAGE_STEP && m->integrator == INT_RK4) {
-        TRY(run_stage(m, d, MJH_STAGE_FORWARD, s, hist_insert));
-        return run_stage(m, d, MJH_STAGE_RUNGEKUTTA4, s, hist_insert);
-      }
-      const bool instrumented = g_instr && g_instr->on;
-      const bool plain = KNOB_ONCE_FLAG("MJH_PLAIN");  // developer knob: one plain kernel per stage, serial
-      if ((instrumented && g_instr->plain) || plain) {
-        // profiling pass: one plain kernel per stage, so that the event pairs time one kernel at a time
-        const int mode = integrator_mode(m);
-        { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, sched_cls_host(*m, *d)); }
-        { Scope sc(K_POS); TRY(launch_pos(m, d, POS_KINEMATICS, POS_CRB, s)); TRY(launch_trn(m, d, s)); }
-        { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
-        { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
-        { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
-        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); }
-        { Scope sc(K_SOLVE); TRY(launch_solve(m, d, s)); }
-        { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s, hist_insert)); }
-        if (stage == MJH_STAGE_STEP) { Scope sc(K_INTEGRATE); TRY(launch_integrate(m, d, mode, s)); }
-        Scope sc(K_OTHER);
-        TRY(launch_publish(m, d, s));
-        TRY(launch_factor_smooth(m, d, m->solver == SOL_NEWTON ? 1 : 0, s));  // CG and PGS write qacc_smooth themselves
-        return MJH_OK;
-      }
+      const bool step = stage == MJH_STAGE_STEP;
+      // MJH_PLAIN: developer knob, one plain kernel per stage, serial
+      if (m->sleep_enabled || KNOB_ONCE_FLAG("MJH_PLAIN") || (run.instr && run.instr->plain)) return run_unfused(m, d, step, m->sleep_enabled != 0, run);
       // fused step: four launches on the caller's stream (see "composite launches" above), as plan_step decides
-      StepPlan p = plan_step(m, d, stage, instrumented);
-      Side* side = p.riders == RIDE_SIDE ? side_stream() : nullptr;
-      if (p.riders == RIDE_SIDE && !side) p = plan_step(m, d, stage, instrumented, false);  // (a failing device: the riders go with the integrator launch)
+      StepPlan p = plan_step(m, d, stage, run.instr != nullptr);
+      Streams* side = p.riders == RIDE_SIDE ? side_streams(run) : nullptr;
+      if (p.riders == RIDE_SIDE && !side) p = plan_step(m, d, stage, run.instr != nullptr, false);  // (a failing device: the riders go with the integrator launch)
       bool sched_done = false;
-      { Scope sc(K_POS); TRY(launch_pos_plus(m, d, POS_KINEMATICS, POS_CRB, &sched_done, s)); }
+      { Scope sc(run, K_POS); TRY(launch_pos_plus(m, d, POS_KINEMATICS, POS_CRB, &sched_done, run)); }
       if (m->trn_general) {
         // k_mid's velocity-stage role is the default instantiation: such a model takes the roles as launches of their own, behind k_transmission
-        { Scope sc(K_POS); TRY(launch_trn(m, d, s)); }
-        if (!sched_done) { Scope sc(K_OTHER); hipLaunchKernelGGL(k_schedule_worlds, dim3(1), dim3(1024), 0, s, *d, sched_cls_host(*m, *d)); }
-        { Scope sc(K_COLLISION); TRY(launch_collision(m, d, s)); }
-        { Scope sc(K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
-        { Scope sc(K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, s)); }
+        { Scope sc(run, K_POS); TRY(launch_trn(m, d, s)); }
+        if (!sched_done) TRY(launch_schedule(m, d, run));
+        TRY(run_mid_unfused(m, d, false, run));
       } else {
-        Scope sc(K_MID);
+        Scope sc(run, K_MID);
         TRY(launch_mid(m, d, !sched_done, s));
       }
-      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 0, s, hist_insert)); }  // (no launch without sensors; before the solver, whose epilogue may integrate the state)
+      { Scope sc(run, K_OTHER); TRY(launch_sensor(m, d, 0, run)); }  // (no launch without sensors; before the solver, whose epilogue may integrate the state)
       if (side) {
         // (tried in round 3: forking the factor after k_fwd_pos, beside k_mid, with qacc_smooth as a separate solve after k_mid -- humanoid
         // Newton + 1.5 %, Panda - 5 %: the extra launch and the slower k_mid cost more than the shorter join wait saves)
         HIPCHK(hipEventRecord(side->fork, s));
-        HIPCHK(hipStreamWaitEvent(side->stream, side->fork, 0));
+        HIPCHK(hipStreamWaitEvent(side->stream[0], side->fork, 0));
         // both riders as roles of ONE launch (k_integrate_plus without integrator workgroups): their two chains overlap and one launch gap
         // goes (round 3, same-box A/B in two interleaved pairs against the two plain kernels of round 2: humanoid Newton 0.2842 -> 0.2829 /
         // 0.2835 -> 0.2822 ms, Panda 142.9 -> 142.0 us; the two-kernel form is retired)
-        TRY(launch_integrate_plus(m, d, p.mode, false, true, side->stream));
-        HIPCHK(hipEventRecord(side->join, side->stream));
+        TRY(launch_integrate_plus(m, d, p.mode, false, true, side->stream[0]));
+        HIPCHK(hipEventRecord(side->join[0], side->stream[0]));
       }
-      { Scope sc(K_SOLVE); TRY(launch_solve_any(m, d, p, s)); }
-      { Scope sc(K_OTHER); TRY(launch_sensor(m, d, 1, s, hist_insert)); }
-      { Scope sc(K_INTEGRATE); TRY(launch_integrate_plus(m, d, p.mode, stage == MJH_STAGE_STEP && !p.fuse_euler, p.riders == RIDE_INTEGRATOR, s)); }
-      if (side) HIPCHK(hipStreamWaitEvent(s, side->join, 0));  // every fork rejoins the caller's stream
+      { Scope sc(run, K_SOLVE); TRY(launch_solve_any(m, d, p, run)); }
+      { Scope sc(run, K_OTHER); TRY(launch_sensor(m, d, 1, run)); }
+      { Scope sc(run, K_INTEGRATE); TRY(launch_integrate_plus(m, d, p.mode, step && !p.fuse_euler, p.riders == RIDE_INTEGRATOR, s)); }
+      if (side) HIPCHK(hipStreamWaitEvent(s, side->join[0], 0));  // every fork rejoins the caller's stream
       return MJH_OK;
     }
     default:
@@ -973,37 +969,38 @@ static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, hipStr
 
 // Every stage goes through here.  A model with delayed actuators (MjhModel.nu_history, csrc/history.hpp) enters forward / step / fwd_actuation through
 // k_history_ctrl: Data.ws_ctrl_delayed = the actuators' buffers read at Data.time (ctrl itself where there is no delay), and everything downstream
-// gets a copy of MjhData whose ctrl points there (as run_sleep_step hands the solver its masked copies).  A step also stores (time, ctrl) in the
-// buffers, once, in that launch: behind the read of the same lane, at the step's own start time.  hist_insert = false (the RK4 sub-evaluations:
+// gets a copy of MjhData whose ctrl points there (as run_unfused hands the solver its masked copies).  A step also stores (time, ctrl) in the
+// buffers, once, in that launch: behind the read of the same lane, at the step's own start time.  run.hist_insert = false (the RK4 sub-evaluations:
 // forward on the perturbed state) keeps every buffer read-only -- the sensors' too, see launch_sensor.
-static int run_stage(const MjhModel* m, const MjhData* d, int stage, hipStream_t s, bool hist_insert) {
-  if (m->nu_history <= 0) return run_stage_impl(m, d, stage, s, hist_insert);
-  if (m->sleep_enabled) return fail(MJH_E_UNSUPPORTED, "actuator delays with sleeping enabled (the wake-by-input test reads ctrl)");
-  if (stage == MJH_STAGE_EULER || stage == MJH_STAGE_IMPLICIT || stage == MJH_STAGE_RUNGEKUTTA4) {
+static int run_stage(const MjhModel* m, const MjhData* d, int stage, Run& run) {
+  const MjhData* dc = d;  // what the stage's launches read: d, or its copy with the delayed ctrl
+  MjhData delayed;
+  if (m->nu_history > 0) {
+    if (m->sleep_enabled) return fail(MJH_E_UNSUPPORTED, "actuator delays with sleeping enabled (the wake-by-input test reads ctrl)");
+    const bool hist = run.hist_insert;
     // the integrator stages of a step taken stage by stage (step1 / step2, forward + rungekutta4): the step's ctrl sample goes in here, at its start time
-    { Scope sc(K_OTHER); TRY(launch_history_ctrl(m, d, hist_insert ? 1 : 0, s)); }
-    if (stage == MJH_STAGE_RUNGEKUTTA4) return run_stage_impl(m, d, stage, s, hist_insert);  // (its forwards come back here with Data.ctrl)
-    MjhData d2 = *d;  // (the implicit integrators differentiate the actuator force: at the delayed ctrl)
-    d2.ctrl = d->ws_ctrl_delayed;
-    return run_stage_impl(m, &d2, stage, s, hist_insert);
+    const bool integ = stage == MJH_STAGE_EULER || stage == MJH_STAGE_IMPLICIT || stage == MJH_STAGE_RUNGEKUTTA4;
+    const bool fwd = stage == MJH_STAGE_FORWARD || stage == MJH_STAGE_STEP || stage == MJH_STAGE_FWD_ACTUATION;
+    if (fwd) apply_noise(m, d, run);  // (k_history_ctrl reads ctrl, in front of any position launch that could carry the noise)
+    // (an RK4 sub-evaluation, FORWARD with hist_insert == false: k_rk4 keeps Data.time at the step's start through all four evaluations, so the delayed
+    // ctrl the first one read -- before the step's sample went in, which with a tight nsample evicted the sample read -- holds for the other three)
+    if (integ || (fwd && (hist || stage != MJH_STAGE_FORWARD))) {
+      Scope sc(run, K_OTHER);
+      TRY(launch_history_ctrl(m, d, hist && (integ || stage == MJH_STAGE_STEP) ? 1 : 0, run.s));
+    }
+    // (the implicit integrators differentiate the actuator force: at the delayed ctrl.  RUNGEKUTTA4 keeps Data.ctrl: its forwards come back here)
+    if (fwd || (integ && stage != MJH_STAGE_RUNGEKUTTA4)) {
+      delayed = *d;
+      delayed.ctrl = d->ws_ctrl_delayed;
+      dc = &delayed;
+    }
   }
-  if (stage != MJH_STAGE_FORWARD && stage != MJH_STAGE_STEP && stage != MJH_STAGE_FWD_ACTUATION) return run_stage_impl(m, d, stage, s, hist_insert);
-  if (g_noise.n > 0) {  // (the benchmark loop's control noise rides with the position launch, behind this one: such a model takes it as a launch of its own)
-    const NoiseArgs noise = g_noise;
-    g_noise.n = 0;
-    Scope sc(K_NOISE);
-    hipLaunchKernelGGL(k_ctrl_noise, dim3((noise.n + 255) / 256), dim3(256), 0, s, *m, *d, noise.center, noise.step, noise.noise_std, noise.noise_rate);
+  // a step with the RK4 integrator = forward + the RUNGEKUTTA4 stage (a sleep-enabled model goes on to run_unfused, which refuses it)
+  if (stage == MJH_STAGE_STEP && m->integrator == INT_RK4 && !m->sleep_enabled) {
+    TRY(run_stage_impl(m, dc, MJH_STAGE_FORWARD, run));
+    return run_stage_impl(m, d, MJH_STAGE_RUNGEKUTTA4, run);
   }
-  // (an RK4 sub-evaluation, hist_insert == false: k_rk4 keeps Data.time at the step's start through all four evaluations, so the delayed ctrl the
-  // first one read -- before the step's sample went in, which with a tight nsample evicted the sample read -- holds for the other three)
-  if (hist_insert || stage != MJH_STAGE_FORWARD) { Scope sc(K_OTHER); TRY(launch_history_ctrl(m, d, stage == MJH_STAGE_STEP && hist_insert ? 1 : 0, s)); }
-  MjhData d2 = *d;
-  d2.ctrl = d->ws_ctrl_delayed;
-  if (stage == MJH_STAGE_STEP && m->integrator == INT_RK4) {
-    TRY(run_stage_impl(m, &d2, MJH_STAGE_FORWARD, s, hist_insert));
-    return run_stage_impl(m, d, MJH_STAGE_RUNGEKUTTA4, s, hist_insert);  // (its forwards come back here with Data.ctrl)
-  }
-  return run_stage_impl(m, &d2, stage, s, hist_insert);
+  return run_stage_impl(m, dc, stage, run);
 }
 
 static int launch_solve_m(const MjhModel* m, const MjhData* d, float* x, const float* y, int mul, hipStream_t s) {
@@ -1040,7 +1037,8 @@ const char* mjh_solver_kernel(const MjhModel* m, const MjhData* d) { return (m &
 
 int mjh_stage(const MjhModel* m, const MjhData* d, int stage, void* stream) {
   TRY(check(m, d));
-  TRY(run_stage(m, d, stage, (hipStream_t)stream));
+  Run run(stream);
+  TRY(run_stage(m, d, stage, run));
   HIPCHK(hipGetLastError());
   return MJH_OK;
 }
@@ -1147,53 +1145,41 @@ int mjh_efc_j_sparse(const MjhModel* m, const MjhData* d, int njmax_nnz, int* ro
 
 int mjh_ctrl_noise(const MjhModel* m, const MjhData* d, const float* ctrl_center, int step, float noise_std, float noise_rate, void* stream) {
   TRY(check(m, d));
-  const int n = d->nworld * m->nu;
-  if (n == 0) return MJH_OK;
-  Scope sc(K_NOISE);
-  hipLaunchKernelGGL(k_ctrl_noise, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, *m, *d, ctrl_center, step, noise_std, noise_rate);
+  Run run(stream);
+  run.noise = NoiseArgs{d->nworld * m->nu, step, noise_std, noise_rate, ctrl_center, 0};
+  apply_noise(m, d, run);
   HIPCHK(hipGetLastError());
   return MJH_OK;
 }
 
 int mjh_release_thread_resources(void) {
-  // the calling thread's side streams and events (one set per device it stepped a Newton model on); the Newton side stream first: it may be
-  // an alias of the first auxiliary stream
+  // the calling thread's side streams and events (one set per device it stepped a Newton or per-island model on)
   int rc = MJH_OK;
   for (int dev = 0; dev < 16; ++dev) {
-    Side* sd = g_side_per_dev[dev];
-    if (!sd) continue;
-    g_side_per_dev[dev] = nullptr;
-    if (hipStreamSynchronize(sd->stream) != hipSuccess) rc = MJH_E_LAUNCH;
-    if (hipEventDestroy(sd->fork) != hipSuccess) rc = MJH_E_LAUNCH;
-    if (hipEventDestroy(sd->join) != hipSuccess) rc = MJH_E_LAUNCH;
-    if (sd->owns_stream && hipStreamDestroy(sd->stream) != hipSuccess) rc = MJH_E_LAUNCH;
-    delete sd;
-  }
-  for (int dev = 0; dev < 16; ++dev) {
-    Aux* a = g_aux_per_dev[dev];
-    if (a) {
-      g_aux_per_dev[dev] = nullptr;
-      for (int k = 0; k < MJH_NAUX; ++k) {
-        if (hipStreamSynchronize(a->stream[k]) != hipSuccess) rc = MJH_E_LAUNCH;
-        if (hipEventDestroy(a->join[k]) != hipSuccess) rc = MJH_E_LAUNCH;
-        if (hipStreamDestroy(a->stream[k]) != hipSuccess) rc = MJH_E_LAUNCH;
-      }
-      if (hipEventDestroy(a->fork) != hipSuccess) rc = MJH_E_LAUNCH;
-      delete a;
+    Streams* a = g_streams_per_dev[dev];
+    if (!a) continue;
+    g_streams_per_dev[dev] = nullptr;
+    for (int k = 0; k < a->n; ++k) {
+      if (hipStreamSynchronize(a->stream[k]) != hipSuccess) rc = MJH_E_LAUNCH;
+      if (hipEventDestroy(a->join[k]) != hipSuccess) rc = MJH_E_LAUNCH;
+      if (hipStreamDestroy(a->stream[k]) != hipSuccess) rc = MJH_E_LAUNCH;
     }
+    if (hipEventDestroy(a->fork) != hipSuccess) rc = MJH_E_LAUNCH;
+    delete a;
   }
   return rc == MJH_OK ? MJH_OK : fail(rc, "mjh_release_thread_resources: %s", "a HIP call failed");
 }
 
 int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** graph_exec_out) {
   TRY(check(m, d));
-  hipStream_t s = (hipStream_t)stream;
+  Run run(stream);
+  const hipStream_t s = run.s;
   // warm the kernels (function attributes must be set outside capture)
-  TRY(run_stage(m, d, MJH_STAGE_STEP, s));
+  TRY(run_stage(m, d, MJH_STAGE_STEP, run));
   HIPCHK(hipStreamSynchronize(s));
   hipGraph_t graph;
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = run_stage(m, d, MJH_STAGE_STEP, s);
+  int rc = run_stage(m, d, MJH_STAGE_STEP, run);
   hipError_t e = hipStreamEndCapture(s, &graph);  // always end the capture so the stream stays usable
   if (rc != MJH_OK) return rc;
   HIPCHK(e);
@@ -1215,36 +1201,33 @@ int mjh_graph_destroy(void* graph_exec) {
 int mjh_timed_steps(const MjhModel* m, const MjhData* d, int nstep, int step0, float noise_std, float noise_rate,
                     void* stream, float* ms_out, float* per_kernel_ms, int plain_kernels) {
   TRY(check(m, d));
-  hipStream_t s = (hipStream_t)stream;
   Instr instr;
-  instr.s = s;
-  instr.on = per_kernel_ms != nullptr;
   instr.plain = plain_kernels != 0;
-  g_instr = &instr;
-  g_serial_solver = instr.on;
-  hipEvent_t t0, t1;
-  HIPCHK(hipEventCreate(&t0));
-  HIPCHK(hipEventCreate(&t1));
-  HIPCHK(hipEventRecord(t0, s));
+  Run run(stream);
+  if (per_kernel_ms) run.instr = &instr;
+  const hipStream_t s = run.s;
+  struct Event {  // (destroyed on every way out)
+    hipEvent_t e = nullptr;
+    ~Event() {
+      if (e) hipEventDestroy(e);
+    }
+  } t0, t1;
+  HIPCHK(hipEventCreate(&t0.e));
+  HIPCHK(hipEventCreate(&t1.e));
+  HIPCHK(hipEventRecord(t0.e, s));
   int rc = MJH_OK;
   for (int i = 0; i < nstep && rc == MJH_OK; ++i) {
-    // the noise of step i rides with that step's first launch (the fused path); the per-kernel profiling passes and the plain
-    // path keep it as its own kernel
+    // the noise of step i is pending in the context (see Run::noise); the per-kernel profiling passes and the plain path keep it as its own kernel
     const bool plain_env = KNOB_ONCE_FLAG("MJH_PLAIN") || KNOB_ONCE_FLAG("MJH_NO_NOISE_FUSION");
-    if (noise_std >= 0.0f && m->nu > 0) {
-      if (instr.on || plain_env) rc = mjh_ctrl_noise(m, d, nullptr, step0 + i, noise_std, noise_rate, stream);
-      else g_noise = NoiseArgs{d->nworld * m->nu, step0 + i, noise_std, noise_rate, nullptr, 0};
-    }
-    if (rc == MJH_OK) rc = run_stage(m, d, MJH_STAGE_STEP, s);
-    g_noise.n = 0;
+    if (noise_std >= 0.0f && m->nu > 0) run.noise = NoiseArgs{d->nworld * m->nu, step0 + i, noise_std, noise_rate, nullptr, 0};
+    if (run.instr || plain_env) apply_noise(m, d, run);
+    rc = run_stage(m, d, MJH_STAGE_STEP, run);
   }
-  hipError_t e = hipEventRecord(t1, s);
-  if (e == hipSuccess) e = hipEventSynchronize(t1);
+  hipError_t e = hipEventRecord(t1.e, s);
+  if (e == hipSuccess) e = hipEventSynchronize(t1.e);
   if (e == hipSuccess) e = instr.err;
-  g_instr = nullptr;
-  g_serial_solver = false;
   float ms = 0.0f;
-  hipEventElapsedTime(&ms, t0, t1);
+  hipEventElapsedTime(&ms, t0.e, t1.e);
   if (ms_out) *ms_out = ms;
   if (per_kernel_ms) {
     for (int k = 0; k < MJH_NKERNEL; ++k) per_kernel_ms[k] = 0.0f;
@@ -1256,8 +1239,6 @@ int mjh_timed_steps(const MjhModel* m, const MjhData* d, int nstep, int step0, f
       hipEventDestroy(instr.ev[2 * i + 1]);
     }
   }
-  hipEventDestroy(t0);
-  hipEventDestroy(t1);
   if (rc != MJH_OK) return rc;
   HIPCHK(e);
   HIPCHK(hipGetLastError());

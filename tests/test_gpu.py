@@ -1052,24 +1052,51 @@ def test_timed_steps_reports_kernel_classes():
   np.testing.assert_allclose(d.time.numpy(), 10 * 0.005, rtol=1e-5)
 
 
-@pytest.mark.parametrize("override", [[], ["opt.solver=cg"], ["opt.integrator=RK4"]])
-def test_timed_steps_equals_noise_plus_step(override):
-  """The benchmark loop (mjh_timed_steps: the control noise rides with the first launch of each fused step) produces bit for
-  bit the trajectory of the API calls ctrl_noise + step, and so does its per-kernel profiling pass (noise as its own kernel)."""
+def _timed_steps_model(name):
+  """A model of test_timed_steps_equals_noise_plus_step: (host model, make_data sizes, start from keyframe 0)."""
+  import test_history
+  import test_sleep
+  import test_transmission
+
+  if name.startswith("delay_"):  # the noise as a launch of its own in front of k_history_ctrl
+    xml = test_history.slide_xml(actuators='<motor joint="j0" delay="0.02" nsample="2"/>', integrator={"delay_euler": "Euler", "delay_rk4": "RK4"}[name])
+    return mjw.mjcf.from_xml_string(xml), {}, False
+  if name == "trn_general":  # the fused step with the middle stages unfused
+    return test_transmission.load("chain"), {}, False
+  if name == "sleep":  # the plain sequence with the sleep bookkeeping: no fused position launch to carry the noise
+    xml = test_sleep.ARM_XML.replace("<worldbody>", '<option><flag sleep="enable" island="enable"/></option><worldbody>', 1)
+    mjm = mjw.mjcf.from_xml_string(xml)
+    assert int(mjm.opt.enableflags) & int(mjw.EnableBit.SLEEP) and mjm.nu == 2
+    return mjm, {}, False
   mjm = mjw.mjcf.load_xml(conftest.HUMANOID_XML)
-  mjw.override_model(mjm, override)
+  mjw.override_model(mjm, {"humanoid": [], "humanoid_cg": ["opt.solver=cg"], "humanoid_rk4": ["opt.integrator=RK4"]}[name])
+  return mjm, dict(nconmax=24, njmax=64), True
+
+
+# plain: the one-plain-kernel-per-stage profiling pass is compared too -- bitwise only where the plain and the fused step share the integrator
+# path (the sleep step IS the plain sequence; the other small models integrate in the integrator launch either way; the humanoid with CG in the solver's epilogue)
+@pytest.mark.parametrize("model,nworld,plain", [
+  pytest.param("humanoid", 300, False, id="override0"), pytest.param("humanoid_cg", 300, False, id="override1"), pytest.param("humanoid_rk4", 300, False, id="override2"),
+  # 3 worlds fill less than one workgroup, 67 leave a ragged last one
+  *[pytest.param(model, nworld, True, id=f"{model}-{nworld}") for model in ("delay_euler", "delay_rk4", "trn_general", "sleep") for nworld in (3, 67)]])
+def test_timed_steps_equals_noise_plus_step(model, nworld, plain):
+  """The benchmark loop (mjh_timed_steps: the control noise rides with the fused position launch of each step, or is launched in front of the
+  first launch that reads ctrl where there is none) produces bit for bit the trajectory of the API calls ctrl_noise + step, and so do its
+  per-kernel profiling passes (noise as its own kernel)."""
+  mjm, sizes, keyframe = _timed_steps_model(model)
   m = mjw.put_model(mjm)
-  da, db, dc = (mjw.make_data(mjm, nworld=300, nconmax=24, njmax=64) for _ in range(3))
-  for d in (da, db, dc):
-    mjw.reset_data_keyframe(m, d, 0)
-  mjw.timed_steps(m, da, 12, step0=3)
-  mjw.timed_steps(m, dc, 12, step0=3, per_kernel=True)
+  want, *got = (mjw.make_data(mjm, nworld=nworld, **sizes) for _ in range(4 if plain else 3))
+  if keyframe:
+    for d in (want, *got):
+      mjw.reset_data_keyframe(m, d, 0)
   for i in range(12):
-    mjw.ctrl_noise(m, db, 3 + i)
-    mjw.step(m, db)
-  for name in ("qpos", "qvel", "ctrl", "qacc_warmstart"):
-    assert (getattr(da, name).numpy() == getattr(db, name).numpy()).all(), name
-    assert (getattr(dc, name).numpy() == getattr(db, name).numpy()).all(), name
+    mjw.ctrl_noise(m, want, 3 + i)
+    mjw.step(m, want)
+  assert mjm.nu > 0 and np.abs(want.ctrl.numpy()).max() > 0
+  for d, kw in zip(got, (dict(), dict(per_kernel=True), dict(per_kernel=True, plain_kernels=True))):
+    mjw.timed_steps(m, d, 12, step0=3, **kw)
+    for name in ("qpos", "qvel", "ctrl", "qacc_warmstart"):
+      assert (getattr(d, name).numpy() == getattr(want, name).numpy()).all(), (kw, name)
 
 
 def test_long_rollout_contact_records_stay_valid():

@@ -592,10 +592,13 @@ def test_knob_table_in_design_md_matches_the_code():
 
 
 def test_launch_decisions_travel_in_the_plan_not_in_globals():
-  """The step plan is passed down explicitly (no thread-local side channels), and the ceil(nv / 4) ladder exists once per lane count (host.hpp)."""
+  """The step plan and the call context are passed down explicitly (no thread-local side channels: the two thread-locals left are per-thread
+  resources, the last-error buffer and the stream set), and the ceil(nv / 4) ladder exists once per lane count (host.hpp)."""
   text = _csrc_text()
+  assert sum(len(re.findall(r"\bthread_local\b", t)) for t in text.values()) == 2
   for f, t in text.items():
     assert not re.search(r"g_fuse_euler|g_newton_inline|g_riders_on_side", t), f
+    assert not re.search(r"g_noise|g_instr|g_serial_solver", t), f
     assert not re.search(r"mjh_knob\(\"", t), f"{f}: a bare mjh_knob(\"...\") read; use knob_* (live) or KNOB_ONCE_* (latched)"
   ladders = sum(len(re.findall(r"switch \(\(m->nv \+ 3\) / 4\)|switch \(nv4\)|if \(nv4 <= 9\)", t)) for t in text.values())
   assert ladders <= 2, ladders
