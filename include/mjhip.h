@@ -454,8 +454,38 @@ int mjh_history_read(const MjhModel* m, const MjhData* d, int is_sensor, int id,
 int mjh_history_init(const MjhModel* m, const MjhData* d, int is_sensor, int id, const float* times, const float* values, int values_stride,
                      const float* phase, void* stream);
 
+/* reset_data / reset_data_keyframe on the device (csrc/reset.hpp; reference io.py reset_data, reset_data_keyframe; additions within ABI v45: neither
+ * MjhModel nor MjhData changed).  What the kernel needs beyond the two structs travels in MjhReset, passed by value to the launch.  World w is
+ * reset when its mask entry is nonzero (both masks NULL: every world) and, with `keys`, when keys[w] is in [0, nkey) (the reference's rule: a
+ * world whose key is out of range is left alone).  It is reset to keyframe keys[w] / `key`, or to qpos0 (keys NULL and key == -1).  Written per
+ * world: qpos, qvel, act, ctrl, qacc_warmstart, qacc, qfrc_applied, xfrc_applied, time, mocap_pos / mocap_quat (the model pose of the mocap
+ * bodies; a keyframe < nkey_mocap then overwrites them), the ten sleep tables, eq_active, the counters nefc, ne, nf, nl, solver_niter, overflow,
+ * ws_ncon, ws_ncollision, and the history buffers in their initial state at the new time.  Without masks and keys also nacon, ncollision and
+ * ws_conadr.  Batched model fields (qpos0, body_pos, body_quat, opt_timestep) are read by the modulo rule.  All pointers are device memory. */
+typedef struct MjhReset {
+  const unsigned char* mask_u8; /* [nworld] one byte per world (bool / uint8), or NULL                                                       */
+  const int* mask_i32;          /* [nworld] int32 mask, or NULL; at most one of the two masks is given                                       */
+  const int* keys;              /* [nworld] keyframe per world, or NULL: `key` for every world                                               */
+  int key;                      /* keys == NULL: the keyframe in [0, nkey), or -1: qpos0                                                      */
+  int nkey;                     /* rows of the key_* tables                                                                                  */
+  int nkey_mocap;               /* rows of key_mpos / key_mquat (0: the model's keyframes carry no mocap poses)                              */
+  const float* key_qpos;        /* [nkey, nq]                                                                                                */
+  const float* key_qvel;        /* [nkey, nv]                                                                                                */
+  const float* key_act;         /* [nkey, na]                                                                                                */
+  const float* key_ctrl;        /* [nkey, nu]                                                                                                */
+  const float* key_mpos;        /* [nkey_mocap, nmocap, 3]                                                                                   */
+  const float* key_mquat;       /* [nkey_mocap, nmocap, 4]                                                                                   */
+  const float* key_time;        /* [nkey]                                                                                                    */
+  const int* eq_active0;        /* [neq]                                                                                                     */
+  const int* mocap_bodyid;      /* [nmocap] the body of each mocap id (the inverse of MjhModel.body_mocapid)                                 */
+} MjhReset;
+int mjh_reset(const MjhModel* m, const MjhData* d, const MjhReset* r, void* stream);
+
 /* hipGraph capture/replay of one step (the reference captures step in a CUDA graph, cli.py:262-265) */
 int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** graph_exec_out);
+/* the same with the reset in front: every launch of the graph first resets the worlds `r` selects (its masks and keys are read by the replay, so
+ * the caller rewrites them on the device between launches), then steps.  The warm-up step runs outside the capture and without the reset. */
+int mjh_graph_create_reset(const MjhModel* m, const MjhData* d, const MjhReset* r, void* stream, void** graph_exec_out);
 int mjh_graph_launch(void* graph_exec, void* stream);
 int mjh_graph_destroy(void* graph_exec);
 

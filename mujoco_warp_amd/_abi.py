@@ -17,9 +17,9 @@ LIB_PATH = os.path.join(_PKG, "libmjhip.so")
 # translation units of the library (compiled in parallel; the solver kernels are ~70 template instantiations) and the
 # headers they include
 UNITS = ["mjhip.hip", "solve_cgp.hip", "solve_cg32.hip", "solve_ell_newton32_r1.hip", "solve_cgw.hip", "solve_newton32.hip", "solve_cg64.hip", "solve_newton64.hip", "solve_ell_cg32.hip", "solve_ell_newton32.hip",
-         "solve_ell_cg64.hip", "solve_ell_newton64.hip", "solve_tree_cg.hip", "solve_tree_newton.hip", "solve_tree_ell_cg.hip", "solve_tree_ell_newton.hip", "pgs_tu.hip", "solve_big.hip", "render_tu.hip", "set_const_tu.hip", "sensor_contact_tu.hip", "sensor_collision_tu.hip", "transmission_tu.hip", "history_tu.hip", "build_id.hip"]
+         "solve_ell_cg64.hip", "solve_ell_newton64.hip", "solve_tree_cg.hip", "solve_tree_newton.hip", "solve_tree_ell_cg.hip", "solve_tree_ell_newton.hip", "pgs_tu.hip", "solve_big.hip", "render_tu.hip", "set_const_tu.hip", "sensor_contact_tu.hip", "sensor_collision_tu.hip", "transmission_tu.hip", "history_tu.hip", "reset_tu.hip", "build_id.hip"]
 HEADERS = ["host.hpp", "solve_tu.hpp", "solve_tree.hpp", "dev_common.hpp", "smooth.hpp", "collide.hpp", "constraint.hpp", "solver.hpp", "solver_cgp.hpp", "solver_cgw.hpp", "solver_newton.hpp", "solver_big.hpp", "pgs.hpp",
-           "integrate.hpp", "implicit.hpp", "pgs_big.hpp", "sleep.hpp", "convex.hpp", "sensor.hpp", "support.hpp", "ray.hpp", "contact_rec.hpp", "render.hpp", "set_const.hpp", "sensor_contact.hpp", "site_inside.hpp", "sensor_collision.hpp", "transmission.hpp", "history.hpp"]
+           "integrate.hpp", "implicit.hpp", "pgs_big.hpp", "sleep.hpp", "convex.hpp", "sensor.hpp", "support.hpp", "ray.hpp", "contact_rec.hpp", "render.hpp", "set_const.hpp", "sensor_contact.hpp", "site_inside.hpp", "sensor_collision.hpp", "transmission.hpp", "history.hpp", "reset.hpp"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 # -fno-slp-vectorize: the SLP vectoriser packs scalar float ops into v_pk_* pairs, which on gfx950 issue at HALF the rate of the
 # scalar forms (tools/ubench.hip: v_pk_fma_f32 4.3 cycles vs v_fma_f32 2.06) and need register pairs plus v_mov shuffles: the Newton
@@ -44,7 +44,7 @@ for _u in UNITS:  # every other solver unit: value-preserving for finite data, s
   if _u.startswith("solve_") and _u not in UNIT_FLAGS:
     UNIT_FLAGS[_u] = _NNAN
 
-_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "unsigned int": ctypes.c_uint}
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "unsigned int": ctypes.c_uint, "unsigned char": ctypes.c_ubyte}
 
 
 def _parse_struct(text, name):
@@ -55,7 +55,7 @@ def _parse_struct(text, name):
     stmt = " ".join(stmt.split())
     if not stmt:
       continue
-    mm = re.match(r"^(const )?(unsigned int|int|float)\s*(\*?)\s*(\w+)$", stmt)
+    mm = re.match(r"^(const )?(unsigned int|unsigned char|int|float)\s*(\*?)\s*(\w+)$", stmt)
     if not mm:
       raise ValueError(f"cannot parse declaration '{stmt}' in struct {name}")
     fields.append((mm.group(4), mm.group(2), bool(mm.group(3))))
@@ -77,6 +77,7 @@ _HEADER_TEXT = open(HEADER).read()
 MODEL_FIELDS = _parse_struct(_HEADER_TEXT, "MjhModel")
 DATA_FIELDS = _parse_struct(_HEADER_TEXT, "MjhData")
 RENDER_FIELDS = _parse_struct(_HEADER_TEXT, "MjhRender")
+RESET_FIELDS = _parse_struct(_HEADER_TEXT, "MjhReset")
 DEFINES = _parse_defines(_HEADER_TEXT)
 FUNCTIONS = _parse_functions(_HEADER_TEXT)
 
@@ -95,6 +96,10 @@ class CData(ctypes.Structure):
 
 class CRender(ctypes.Structure):
   _fields_ = _mk(RENDER_FIELDS)
+
+
+class CReset(ctypes.Structure):
+  _fields_ = _mk(RESET_FIELDS)
 
 
 def source_build_id():
@@ -255,7 +260,9 @@ def lib():
   L.mjh_history_init.argtypes = [mp, dp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]
   L.mjh_efc_j_sparse.argtypes = [mp, dp, ctypes.c_int, vp, vp, vp, vp, vp]
   L.mjh_ctrl_noise.argtypes = [mp, dp, vp, ctypes.c_int, ctypes.c_float, ctypes.c_float, vp]
+  L.mjh_reset.argtypes = [mp, dp, ctypes.POINTER(CReset), vp]
   L.mjh_graph_create.argtypes = [mp, dp, vp, ctypes.POINTER(vp)]
+  L.mjh_graph_create_reset.argtypes = [mp, dp, ctypes.POINTER(CReset), vp, ctypes.POINTER(vp)]
   L.mjh_ws_ccd_floats.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
   L.mjh_graph_launch.argtypes = [vp, vp]
   L.mjh_graph_destroy.argtypes = [vp]

@@ -14,6 +14,7 @@
 //   transmission_tu.hip (k_transmission, k_fwd_vel_trn: general actuator transmissions, only for models with MjhModel.trn_general),
 //   history_tu.hip (k_history_ctrl, k_history_sensor, k_history_read, k_history_init and the entry points mjh_history_read / mjh_history_init:
 //   actuator and sensor delays, only for models with MjhModel.nhistory > 0),
+//   reset_tu.hip (k_reset and its entry point mjh_reset: reset_data / reset_data_keyframe on the device; never launched by a step),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
@@ -182,3 +183,5 @@ int launch_vel_trn(const MjhModel* m, const MjhData* d, int first, int last, boo
 // Data.time (insert: and ctrl into them), and behind the sensor launch of `stage` the delayed read / insert of that stage's sensors with a buffer
 int launch_history_ctrl(const MjhModel* m, const MjhData* d, int insert, hipStream_t s);
 int launch_history_sensor(const MjhModel* m, const MjhData* d, int stage, int insert, hipStream_t s);
+// reset of the worlds `r` selects (reset.hpp, reset_tu.hip): mjh_reset, and the first node of the graph of mjh_graph_create_reset
+int launch_reset(const MjhModel* m, const MjhData* d, const MjhReset* r, hipStream_t s);

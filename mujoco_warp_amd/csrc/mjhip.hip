@@ -1170,7 +1170,8 @@ int mjh_release_thread_resources(void) {
   return rc == MJH_OK ? MJH_OK : fail(rc, "mjh_release_thread_resources: %s", "a HIP call failed");
 }
 
-int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** graph_exec_out) {
+// the graph of one step; reset != nullptr: with k_reset in front of it, on the same stream (one more node of the linear chain, no branch)
+static int graph_create(const MjhModel* m, const MjhData* d, const MjhReset* reset, void* stream, void** graph_exec_out) {
   TRY(check(m, d));
   Run run(stream);
   const hipStream_t s = run.s;
@@ -1179,7 +1180,8 @@ int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** g
   HIPCHK(hipStreamSynchronize(s));
   hipGraph_t graph;
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = run_stage(m, d, MJH_STAGE_STEP, run);
+  int rc = reset ? launch_reset(m, d, reset, s) : MJH_OK;  // (k_reset sets no kernel attribute: nothing to warm)
+  if (rc == MJH_OK) rc = run_stage(m, d, MJH_STAGE_STEP, run);
   hipError_t e = hipStreamEndCapture(s, &graph);  // always end the capture so the stream stays usable
   if (rc != MJH_OK) return rc;
   HIPCHK(e);
@@ -1188,6 +1190,11 @@ int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** g
   hipGraphDestroy(graph);
   *graph_exec_out = (void*)exec;
   return MJH_OK;
+}
+int mjh_graph_create(const MjhModel* m, const MjhData* d, void* stream, void** graph_exec_out) { return graph_create(m, d, nullptr, stream, graph_exec_out); }
+int mjh_graph_create_reset(const MjhModel* m, const MjhData* d, const MjhReset* r, void* stream, void** graph_exec_out) {
+  if (!r) return fail(MJH_E_ARG, "mjh_graph_create_reset: null reset arguments");
+  return graph_create(m, d, r, stream, graph_exec_out);
 }
 int mjh_graph_launch(void* graph_exec, void* stream) {
   HIPCHK(hipGraphLaunch((hipGraphExec_t)graph_exec, (hipStream_t)stream));

@@ -287,13 +287,24 @@ def ctrl_noise(m, d, step_index: int, noise_std: float = 0.01, noise_rate: float
 
 
 class StepGraph:
-  """hipGraph of one `step` (the reference captures step in a CUDA graph: cli.py:262-265)."""
+  """hipGraph of one `step` (the reference captures step in a CUDA graph: cli.py:262-265).
 
-  def __init__(self, m, d):
+  StepGraph(m, d, reset=mask): an auto-resetting step.  `reset` is a per-world mask on the device (DeviceArray or tensor [nworld] of dtype bool,
+  uint8, int8 or int32, contiguous); every launch() first resets the worlds whose entry is nonzero -- as reset_data does, or, with `key` (a
+  device int32 array [nworld]), as reset_data_keyframe does -- and then steps.  The graph reads the mask and the keys where they are: the
+  caller rewrites them in place between launches (`mask.t.copy_(done)`), with device operations."""
+
+  def __init__(self, m, d, reset=None, key=None):
     self._m, self._d = m, d  # keep the buffers alive
     self._exec = ctypes.c_void_p()
     L = _abi.lib()
     _stream()  # raises without a GPU
+    creset = None
+    if reset is None:
+      if key is not None:
+        raise ValueError("StepGraph: `key` needs a `reset` mask")
+    else:
+      creset, self._reset_keep = self._reset_args(m, d, reset, key)
     # stream capture is illegal on the legacy default stream: capture on a side stream ordered after the current one
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -303,11 +314,31 @@ class StepGraph:
     # sleeping models: the warm-up step would advance the sleep counters / wake state / island tables by one step
     names += ["tree_asleep", "tree_awake", "body_awake", "body_awake_ind", "dof_awake_ind", "ntree_awake", "nbody_awake", "nv_awake", "tree_island", "nisland"]
     keep = {k: getattr(d, k).t.clone() for k in names if getattr(d, k, None) is not None and getattr(d, k).size}
-    rc = L.mjh_graph_create(ctypes.byref(io.c_model(m)), ctypes.byref(io.c_data(d)), ctypes.c_void_p(side.cuda_stream), ctypes.byref(self._exec))
+    if creset is None:
+      rc = L.mjh_graph_create(ctypes.byref(io.c_model(m)), ctypes.byref(io.c_data(d)), ctypes.c_void_p(side.cuda_stream), ctypes.byref(self._exec))
+    else:  # (the warm-up step runs without the reset; the capture is [reset][step])
+      rc = L.mjh_graph_create_reset(ctypes.byref(io.c_model(m)), ctypes.byref(io.c_data(d)), ctypes.byref(creset), ctypes.c_void_p(side.cuda_stream),
+                                    ctypes.byref(self._exec))
     torch.cuda.current_stream().wait_stream(side)
     for k, v in keep.items():
       getattr(d, k).t.copy_(v)
     _abi.check(rc)
+
+  @staticmethod
+  def _reset_args(m, d, reset, key):
+    """MjhReset of the captured reset: the graph keeps the addresses, so the mask and the keys must be the caller's own device memory."""
+    device = d.time.t.device
+
+    def own(x, what, dtypes):
+      t = io._per_world(x, d.nworld, what, torch.bool in dtypes)
+      if not isinstance(t, torch.Tensor) or t.device != device or t.dtype not in dtypes or not t.is_contiguous():
+        raise ValueError(f"StepGraph: {what} must be a contiguous DeviceArray or tensor on {device} of dtype {' / '.join(str(x) for x in dtypes)} "
+                         f"(the graph reads it in place at every launch)")
+      return t
+
+    mask = own(reset, "reset", (torch.bool, torch.uint8, torch.int8, torch.int32))
+    keys = None if key is None else own(key, "key", (torch.int32,))
+    return io.c_reset(m, d, mask, keys, -1)
 
   def launch(self):
     _abi.check(_abi.lib().mjh_graph_launch(self._exec, _stream()))

@@ -738,6 +738,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   for name, width in (("key_qpos", m.nq), ("key_qvel", nv), ("key_ctrl", m.nu), ("key_mpos", 3 * m.nmocap), ("key_mquat", 4 * m.nmocap), ("key_act", m.na)):
     setattr(m, name, _arr(getattr(mjm, name, np.zeros((0, width))), np.float32))
   m.key_time = _arr(getattr(mjm, "key_time", np.zeros(0)), np.float32)
+  _build_reset_tables(m, host["body_mocapid"])
   m._dirty = True
   m._c = None
   return m
@@ -821,6 +822,7 @@ def c_model(m: types.Model):
         setattr(c, name + "_nb", src.shape[0])
     elif not name.endswith("_nb"):
       setattr(c, name, _C_MODEL_SCALARS[name](m) if name in _C_MODEL_SCALARS else int(getattr(m, name)))
+  _reset_tables(m)  # (a field was re-bound: the device copies of the keyframe tables follow when it was one of theirs)
   object.__setattr__(m, "_c", c)
   object.__setattr__(m, "_dirty", False)
   return c
@@ -1104,69 +1106,231 @@ def state_size(m: types.Model, sig: int) -> int:
   return int(sum(n for bit, n in sizes.items() if sig & int(bit)))
 
 
+def _active_mask(active, nworld, device):
+  """`active` as a bool tensor [nworld, 1] on `device`.  A DeviceArray or a tensor stays on the device (no host trip); anything else is read
+  as a host array of truth values and uploaded."""
+  import torch
+
+  t = active.t if isinstance(active, DeviceArray) else active
+  if isinstance(t, torch.Tensor):
+    t = (t if t.dtype == torch.bool else t.ne(0)).to(device)
+  else:
+    t = torch.as_tensor(np.asarray(t, dtype=bool), device=device)
+  if tuple(t.shape) != (nworld,):
+    raise ValueError(f"active must have shape ({nworld},), got {tuple(t.shape)}")
+  return t.reshape(nworld, 1)
+
+
 def get_state(m: types.Model, d: types.Data, state: DeviceArray, sig: int, active=None):
   """Copies the concatenated state components selected by sig (types.State bits) from Data into state [nworld, state_size(m, sig)]
-  (reference support.get_state, support.py:674); `active` is an optional per-world mask.  Device-to-device copies."""
+  (reference support.get_state, support.py:674); `active` is an optional per-world mask (host array, DeviceArray or tensor).  Device-to-device
+  copies; a mask on the device is used where it is."""
   import torch
 
   if tuple(state.shape) != (d.nworld, state_size(m, int(sig))):  # (checked before anything is written)
     raise ValueError(f"state must have shape ({d.nworld}, {state_size(m, int(sig))})")
-  mask = None if active is None else torch.as_tensor(np.asarray(active.numpy() if hasattr(active, "numpy") else active, dtype=bool), device=state.t.device)
+  mask = None if active is None else _active_mask(active, d.nworld, state.t.device)
   adr = 0
   for arr, n in _state_fields(m, d, int(sig)):
     src = arr.t.reshape(d.nworld, n).to(state.t.dtype)
     dst = state.t[:, adr : adr + n]
-    if mask is None:
-      dst.copy_(src)
-    else:
-      dst[mask] = src[mask]
+    dst.copy_(src if mask is None else torch.where(mask, src, dst))
     adr += n
 
 
 def set_state(m: types.Model, d: types.Data, state: DeviceArray, sig: int, active=None):
-  """Copies the concatenated state components selected by sig from state into Data (reference support.set_state, support.py:829)."""
+  """Copies the concatenated state components selected by sig from state into Data (reference support.set_state, support.py:829); `active` as
+  in get_state."""
   import torch
 
   if tuple(state.shape) != (d.nworld, state_size(m, int(sig))):
     raise ValueError(f"state must have shape ({d.nworld}, {state_size(m, int(sig))})")
-  mask = None if active is None else torch.as_tensor(np.asarray(active.numpy() if hasattr(active, "numpy") else active, dtype=bool), device=state.t.device)
+  mask = None if active is None else _active_mask(active, d.nworld, state.t.device)
   adr = 0
   for arr, n in _state_fields(m, d, int(sig)):
     dst = arr.t.reshape(d.nworld, n)
     src = state.t[:, adr : adr + n].to(dst.dtype)
-    if mask is None:
-      dst.copy_(src)
-    else:
-      dst[mask] = src[mask]
+    dst.copy_(src if mask is None else torch.where(mask, src, dst))
     adr += n
 
 
+# ---- reset_data / reset_data_keyframe ---------------------------------------------------------------------------------------------------
+# On a GPU the whole reset is ONE launch of csrc/reset.hpp on the current stream: a mask or a key array that lives on the device is read where it
+# is, nothing is copied to the host and nothing synchronises, so the call can sit in an RL loop (and in a captured graph: forward.StepGraph).
+# On the CPU device (host-logic tests only) the numpy code below does the same edits.
+#
+# The kernel reads device copies of the keyframe tables and of eq_active0 (host numpy attributes of Model).  They are made at put_model and
+# follow a re-binding (`m.key_qpos = new_table`: the _Dirty flag makes c_model look again).  An IN-PLACE edit of a host table
+# (`m.key_qpos[0, 2] = 1.0`) is not seen: re-bind the attribute (`m.key_qpos = m.key_qpos.copy()`).
+_RESET_HOST_TABLES = {"key_qpos": np.float32, "key_qvel": np.float32, "key_act": np.float32, "key_ctrl": np.float32, "key_mpos": np.float32,
+                      "key_mquat": np.float32, "key_time": np.float32, "eq_active0": np.int32}
+
+
+def _build_reset_tables(m, body_mocapid=None):
+  """Device copies of the host tables a reset reads, kept on the Model together with the host arrays they were made from.  body_mocapid: the
+  host array at put_model; later rebuilds keep the mocap body list (the body tables are not re-bound field by field)."""
+  src = tuple(getattr(m, name, None) for name in _RESET_HOST_TABLES)
+  dev = {name: DeviceArray.from_numpy(np.zeros(0) if a is None else a, dtype=dtype) for (name, dtype), a in zip(_RESET_HOST_TABLES.items(), src)}
+  prev = getattr(m, "_reset_dev", None)
+  if body_mocapid is None and prev is not None:
+    dev["mocap_bodyid"] = prev[1]["mocap_bodyid"]
+  else:
+    mid = np.asarray(m.body_mocapid.numpy() if body_mocapid is None else body_mocapid).reshape(-1)
+    dev["mocap_bodyid"] = DeviceArray.from_numpy(np.flatnonzero(mid >= 0)[np.argsort(mid[mid >= 0], kind="stable")], dtype=np.int32)  # mocap-id order
+  object.__setattr__(m, "_reset_dev", (src, dev))
+  return dev
+
+
+def _reset_tables(m):
+  """{name: DeviceArray} of the keyframe tables, eq_active0 and the mocap body list; rebuilt when one of the host tables was re-bound."""
+  cur = getattr(m, "_reset_dev", None)
+  if cur is not None and all(getattr(m, name, None) is a for name, a in zip(_RESET_HOST_TABLES, cur[0])):
+    return cur[1]
+  return _build_reset_tables(m)
+
+
+def _nkey_mocap(m):
+  """Keyframes that carry mocap poses (a host model without key_mpos / key_mquat: none)."""
+  if not m.nmocap or getattr(m, "key_mpos", None) is None or getattr(m, "key_mquat", None) is None:
+    return 0
+  return min(len(m.key_mpos), len(m.key_mquat), int(m.nkey))
+
+
+def _per_world(x, nworld, what, allow_bool):
+  """x -- a numpy array (or anything numpy reads), a DeviceArray or a torch tensor -- checked to be [nworld] of an integer dtype (or bool,
+  when allowed); returns the numpy array or the tensor."""
+  import torch
+
+  t = x.t if isinstance(x, DeviceArray) else x
+  if isinstance(t, torch.Tensor):
+    kind = "b" if t.dtype == torch.bool else "f" if (t.dtype.is_floating_point or t.dtype.is_complex) else "i"
+  else:
+    t = np.asarray(t)
+    kind = {"u": "i"}.get(t.dtype.kind, t.dtype.kind)
+  if kind != "i" and not (allow_bool and kind == "b"):
+    raise ValueError(f"{what} must be of {'bool or ' if allow_bool else ''}integer dtype, got {t.dtype}")
+  if tuple(t.shape) != (nworld,):
+    raise ValueError(f"{what} must have shape ({nworld},), got {tuple(t.shape)}")
+  return t
+
+
+def _host(t):
+  return t if isinstance(t, np.ndarray) else t.detach().cpu().numpy()
+
+
+def _device_mask(t, device):
+  """The checked mask as a contiguous device tensor of one of the dtypes the kernel reads (1-byte or int32 entries)."""
+  import torch
+
+  if isinstance(t, np.ndarray):
+    return torch.from_numpy(np.ascontiguousarray(t != 0)).to(device)
+  if t.dtype not in (torch.bool, torch.uint8, torch.int8, torch.int32):
+    t = t.ne(0)
+  return t.to(device).contiguous()
+
+
+def _device_keys(t, nkey, device):
+  """The checked per-world keys as a contiguous int32 device tensor (wider integers are clamped to [-1, nkey] first: out of range stays out of range)."""
+  import torch
+
+  if isinstance(t, np.ndarray):
+    return torch.from_numpy(np.clip(t, -1, nkey).astype(np.int32)).to(device)
+  if t.dtype != torch.int32:
+    t = t.clamp(-1, nkey).to(torch.int32)
+  return t.to(device).contiguous()
+
+
+def c_reset(m, d, mask=None, keys=None, key=-1):
+  """ctypes MjhReset for a reset of `d`: mask / keys are device tensors as _device_mask / _device_keys return them (or None), `key` the scalar
+  keyframe (-1: qpos0).  Returns (struct, what it points to -- to be kept alive while a launch or a graph may read it)."""
+  import torch
+
+  tabs = _reset_tables(m)
+  if keys is not None or key >= 0:  # (the kernel indexes the tables with keys below nkey: a host model that brought fewer rows must not get that far)
+    for name, width in (("key_qpos", m.nq), ("key_qvel", m.nv), ("key_act", m.na), ("key_ctrl", m.nu), ("key_time", 1)):
+      if width and tabs[name].size != int(m.nkey) * width:
+        raise ValueError(f"Model.{name} has {tabs[name].size} entries, expected nkey x {width} = {int(m.nkey) * width}")
+    nkm = _nkey_mocap(m)
+    if tabs["key_mpos"].size < nkm * 3 * m.nmocap or tabs["key_mquat"].size < nkm * 4 * m.nmocap:
+      raise ValueError(f"Model.key_mpos / key_mquat do not hold {nkm} keyframes of {m.nmocap} mocap poses")
+  if m.neq and tabs["eq_active0"].size != int(m.neq):
+    raise ValueError(f"Model.eq_active0 has {tabs['eq_active0'].size} entries, expected neq = {int(m.neq)}")
+  r = _abi.CReset()
+  ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+  if mask is not None:
+    if mask.dtype == torch.int32:
+      r.mask_i32 = ptr(mask)
+    else:
+      r.mask_u8 = ptr(mask)
+  r.keys = ptr(keys)
+  r.key, r.nkey, r.nkey_mocap = int(key), int(m.nkey), _nkey_mocap(m)
+  for name in (*_RESET_HOST_TABLES, "mocap_bodyid"):
+    setattr(r, name, tabs[name].ptr or None)
+  return r, (tabs, mask, keys)
+
+
+def _reset_device(m, d, mask, keys, key):
+  from .forward import _stream
+
+  device = d.time.t.device
+  mask = None if mask is None else _device_mask(mask, device)
+  keys = None if keys is None else _device_keys(keys, int(m.nkey), device)
+  r, keep = c_reset(m, d, mask, keys, key)
+  _abi.check(_abi.lib().mjh_reset(ctypes.byref(c_model(m)), ctypes.byref(c_data(d)), ctypes.byref(r), _stream()))
+  # (`keep`: tensors made here are freed on return; torch's allocator hands their memory out again in stream order, behind the launch)
+
+
+def _on_gpu(d):
+  return d.time.t.device.type != "cpu"
+
+
 def reset_data(m: types.Model, d: types.Data, reset=None):
-  """Resets data to qpos0 (reference io.py:2435); `reset` is an optional per-world bool mask."""
-  mask = None if reset is None else np.asarray(reset.numpy() if hasattr(reset, "numpy") else reset, dtype=bool)
+  """Resets data to qpos0 (reference io.py:2435).  `reset`: optional per-world mask [nworld] of bool or integer dtype -- a numpy array, a
+  DeviceArray or a torch tensor; nonzero entries are reset.  On a GPU: one launch on the current stream, no synchronisation; only a numpy mask
+  is uploaded."""
+  mask = None if reset is None else _per_world(reset, d.nworld, "reset", True)
+  if _on_gpu(d):
+    return _reset_device(m, d, mask, None, -1)
+  mask = None if mask is None else _host(mask) != 0
   _reset_state(m, d, np.tile(m.qpos0.numpy()[:1], (d.nworld, 1)) if m.qpos0.shape[0] == 1 else m.qpos0.numpy()[np.arange(d.nworld) % m.qpos0.shape[0]],
                None, None, None, 0.0, mask)
 
 
-def reset_data_keyframe(m: types.Model, d: types.Data, key: int, reset=None):
-  """Resets data to keyframe `key` (reference io.py:2797)."""
-  if key < 0 or key >= m.nkey:
-    raise ValueError(f"keyframe {key} out of range [0, {m.nkey})")
-  mask = None if reset is None else np.asarray(reset.numpy() if hasattr(reset, "numpy") else reset, dtype=bool)
+def reset_data_keyframe(m: types.Model, d: types.Data, key, reset=None):
+  """Resets data to keyframe `key` (reference io.py:2797).  `key`: an int (out of range: ValueError), or one keyframe per world [nworld] of integer
+  dtype (numpy array, DeviceArray or torch tensor) -- a world whose key is outside [0, nkey) is not reset.  `reset` as in reset_data; a world is
+  reset when both select it.  The keyframe tables are read from their device copies: after an in-place edit of m.key_* re-bind the attribute."""
+  keys = None
+  if isinstance(key, (int, np.integer)):
+    key = int(key)
+    if key < 0 or key >= m.nkey:
+      raise ValueError(f"keyframe {key} out of range [0, {m.nkey})")
+  else:
+    keys, key = _per_world(key, d.nworld, "key", False), -1
+  mask = None if reset is None else _per_world(reset, d.nworld, "reset", True)
+  if _on_gpu(d):
+    return _reset_device(m, d, mask, keys, key)
+  mask = None if mask is None else _host(mask) != 0
   W = d.nworld
-  _reset_state(m, d, np.tile(m.key_qpos[key], (W, 1)), np.tile(m.key_qvel[key], (W, 1)),
-               np.tile(m.key_act[key], (W, 1)) if m.na else None, np.tile(m.key_ctrl[key], (W, 1)) if m.nu else None,
-               float(m.key_time[key]), mask)
-  if m.nmocap and getattr(m, "key_mpos", None) is not None and len(m.key_mpos) > key:  # keyframe mocap poses (io.py:2855)
+  if keys is None:
+    k, time = np.full(W, key), float(m.key_time[key])
+  else:
+    keys = _host(keys)
+    valid = (keys >= 0) & (keys < m.nkey)
+    mask = valid if mask is None else mask & valid  # (a mask even when every key is valid: the per-world form never touches the global counters)
+    if not mask.any():
+      return
+    k = np.where(valid, keys, 0)
+    time = np.asarray(m.key_time, dtype=np.float32)[k]
+  _reset_state(m, d, m.key_qpos[k], m.key_qvel[k], m.key_act[k] if m.na else None, m.key_ctrl[k] if m.nu else None, time, mask)
+  nkm = _nkey_mocap(m)
+  if nkm and (k < nkm).any():  # keyframe mocap poses (io.py:2855)
+    sel = (k < nkm) if mask is None else mask & (k < nkm)
     for name, src, width in (("mocap_pos", m.key_mpos, 3), ("mocap_quat", m.key_mquat, 4)):
-      val = np.tile(np.asarray(src[key], dtype=np.float32).reshape(1, m.nmocap, width), (W, 1, 1))
-      dst = getattr(d, name)
-      if mask is None:
-        dst.assign(val)
-      else:
-        cur = dst.numpy().copy()
-        cur[mask] = val[mask]
-        dst.assign(cur)
+      val = np.asarray(src, dtype=np.float32).reshape(len(src), m.nmocap, width)[np.minimum(k, nkm - 1)]
+      cur = getattr(d, name).numpy().copy()
+      cur[sel] = val[sel]
+      getattr(d, name).assign(cur)
 
 
 def _reset_mocap(m, d, mask):
@@ -1210,12 +1374,16 @@ def _reset_sleep(m, d, mask):
 
 
 def _reset_history(m, d, mask, time):
-  """Data.history of the worlds in `mask` (None: all) in its initial state at `time` (mjcf.history_row; the timestep is the world's own)."""
+  """Data.history of the worlds in `mask` (None: all) in its initial state at `time` (a scalar, or one per world; mjcf.history_row; the
+  timestep is the world's own)."""
   if not m.nhistory:
     return
   h = m.opt.timestep.numpy().reshape(-1).astype(np.float64)
-  rows = np.stack([history_row(m._history_buffers, m.nhistory, float(time), hw) for hw in h]).astype(np.float32)
-  val = rows[np.arange(d.nworld) % len(h)]
+  if np.ndim(time) == 0:
+    rows = np.stack([history_row(m._history_buffers, m.nhistory, float(time), hw) for hw in h]).astype(np.float32)
+    val = rows[np.arange(d.nworld) % len(h)]
+  else:  # (one time per world: the per-world keyframes)
+    val = np.stack([history_row(m._history_buffers, m.nhistory, float(time[w]), h[w % len(h)]) for w in range(d.nworld)]).astype(np.float32)
   if mask is not None:
     cur = d.history.numpy().copy()
     cur[mask] = val[mask]
