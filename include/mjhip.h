@@ -244,6 +244,8 @@ typedef struct MjhModel {
   int trn_general;              /* 1: some actuator's moment row is not the scalar gear[0] of a hinge / slide joint: k_transmission runs behind the
                                    position stage and the velocity stage takes its general instantiation (sparse moment rows) */
   int nJmom;                    /* entries of all moment rows (reference types.py Model.nJmom); nu when trn_general == 0 */
+  int has_connect;              /* (equality block below; here it fills padding) 1: some equality is a connect: forward / step take the unfused
+                                   stage order with the velocity kinematics (cvel, cdof_dot) in front of the constraint rows */
   const int* actuator_trntype;  /* [nu] TrnType: 0 joint, 1 jointinparent, 4 site */
   const int* actuator_trnobj;   /* [nu, 2] Model.actuator_trnid: joint | site, refsite or -1 */
   const int* moment_rownnz; const int* moment_rowadr; /* [nu] the rows of Data.actuator_moment [nworld, nJmom], actuator order */
@@ -252,7 +254,13 @@ typedef struct MjhModel {
   const int* moment_side;       /* [nJmom] site rows: 1 the dof moves the site only, 2 the refsite only (its entry is subtracted); 0 joint rows */
   const int* momentT_adr;       /* [nv + 1] the transpose, dof-major: dof i owns entries momentT_adr[i] .. momentT_adr[i + 1] of */
   const int* momentT_act; const int* momentT_ind; /* [nJmom] actuator and index into its world's actuator_moment, ascending actuator */
-  /* equality constraints: joint couplings only (constraint.py:500-640); eq_data = polycoef[0..4] */
+  /* equality constraints: joint couplings (constraint.py:500-640; eq_data = polycoef[0..4]) and connects (constraint.py:156-496; eq_data =
+     anchor in body 1's frame [0..2], in body 2's frame [3..5]; ids are bodies, or sites whose positions are the anchors).  eq_kind
+     (and has_connect, above) are an addition within ABI v45 that is NOT at the tail: the offsets of every later field move.  ONE pointer, and
+     has_connect in what was padding: the struct grows by 8 bytes, which every k_mid instantiation takes without a byte of scratch (two
+     pointers cost the height-field instantiations 16 bytes each). */
+  const int* eq_kind;           /* [2, neq] row 0: Model.eq_type (mjtEq: 0 connect, 2 joint); row 1: Model.eq_objtype (mjtObj of obj1id /
+                                   obj2id: 1 body, 6 site, 3 joint) */
   const int* eq_obj1id; const int* eq_obj2id;
   const float* eq_solref; int eq_solref_nb;
   const float* eq_solimp; int eq_solimp_nb;

@@ -2,11 +2,11 @@
 //
 // Reference: constraint.py:84-153 (_efc_row), 1766-1865 (_friction_dof), 1991-2105 (_limit_slide_hinge),
 // 2107-2240 (_limit_ball), 2641-2757 (_efc_contact_init), 3751-3879 (_efc_contact_jac_dense),
-// 4197-4343 (_efc_contact_update); support.py:488-533 (jac helpers).
+// 4197-4343 (_efc_contact_update); support.py:488-533 (jac helpers); 156-496 (_equality_connect), 500-640 (_equality_joint).
 //
 // MI355X mapping: the reference allocates rows with per-world atomics from five separate launches (row order
 // nondeterministic).  Here rows are allocated with ballot/prefix compaction in MuJoCo's canonical order
-// (dof friction, joint limits, contacts in contact order), J rows are written with lanes mapped to dofs
+// (equalities in id order, dof friction, joint limits, contacts in contact order), J rows are written with lanes mapped to dofs
 // (coalesced 128 B row segments), and J*qvel comes from DPP/permute group reductions -- no atomics at all.
 #pragma once
 #include "dev_common.hpp"
@@ -104,7 +104,102 @@ DEV void csum_n(float (&v)[N]) {
   }
 }
 
+// ---- connect equalities (constraint.py:156-496) ---------------------------------------------------------------------------------------
+// A connect pins a point of body 1 to a point of body 2: three rows, pos = p1 - p2, J = jacp(b1, p1) - jacp(b2, p2), and the reference
+// acceleration corrected by -Jdot qvel (constraint.py:494; Jdot per dof: support.py:615-671 jac_dot_dof).  The lane group walks the
+// dofs, lane = dof: coalesced row stores, and J qvel / Jdot qvel are two 3-vector sums over the group (csum_n: DPP, fixed order, no
+// atomics).  Reads Data.cvel / cdof_dot: the velocity kinematics of the CURRENT state run in front of this kernel (mjhip.hip run_unfused).
+struct ConnectSide {
+  int body;
+  V3 point, off, pvel;  // anchor in the world; the same from the subtree com of the body's root; velocity of the body's point there
+};
+DEV ConnectSide connect_side(const MjhModel& m, const MjhData& d, int w, bool site, int obj, V3 anchor, const float* scom, const int* broot) {
+  ConnectSide s;
+  if (site) {
+    s.body = m.site_bodyid[obj];
+    s.point = ld3(d.site_xpos + ((size_t)w * m.nsite + obj) * 3);
+  } else {
+    s.body = obj;
+    s.point = ld3(d.xpos + ((size_t)w * m.nbody + obj) * 3) + mat_mul(d.xmat + ((size_t)w * m.nbody + obj) * 9, anchor);
+  }
+  s.off = s.point - ld3(scom + 3 * broot[s.body]);
+  const float* cv = d.cvel + ((size_t)w * m.nbody + s.body) * 6;
+  s.pvel = ld3(cv + 3) - cross(s.off, ld3(cv));
+  return s;
+}
+// rows r .. r + 2 of connect e (the caller has checked that they fit); every lane of the group takes part
 template <int G>
+DEV void connect_rows(const MjhModel& m, const MjhData& d, int w, int e, int r, int lig, float timestep, const float* cdof, const float* qvel,
+                      const float* scom, const int* broot, const unsigned* bmask, float* J) {
+  const int nv = m.nv, nvp = d.nv_pad, neq = m.neq, nw = (nv + 31) / 32;
+  const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * neq) + 11 * e;
+  const bool site = m.eq_kind[neq + e] == EQ_OBJ_SITE;
+  const ConnectSide s1 = connect_side(m, d, w, site, m.eq_obj1id[e], ld3(data), scom, broot);
+  const ConnectSide s2 = connect_side(m, d, w, site, m.eq_obj2id[e], ld3(data + 3), scom, broot);
+  const V3 pos = s1.point - s2.point;
+  float jv[3] = {0.0f, 0.0f, 0.0f}, jdv[3] = {0.0f, 0.0f, 0.0f};  // this lane's share of J qvel and Jdot qvel
+  for (int i0 = 0; i0 < nvp; i0 += G) {
+    const int i = i0 + lig;
+    V3 jp = V3{0, 0, 0}, jd = V3{0, 0, 0};
+    float qv = 0.0f;
+    if (i < nv) {
+      const bool a1 = bmask[s1.body * nw + (i >> 5)] & (1u << (i & 31));
+      const bool a2 = bmask[s2.body * nw + (i >> 5)] & (1u << (i & 31));
+      qv = qvel[i];
+      if (a1 || a2) {
+        const V3 ang = ld3(cdof + 6 * i), lin = ld3(cdof + 6 * i + 3);
+        // d/dt of the dof's motion axis: Data.cdof_dot, but for the rotational dofs of ball and free joints the cross product with the
+        // velocity of the dof's own body (jac_dot_dof's quaternion branch)
+        float cd[6];
+        const int j = m.dof_jntid[i], jt = m.jnt_type[j];
+        if (jt == JNT_BALL || (jt == JNT_FREE && i >= m.jnt_dofadr[j] + 3))
+          motion_cross(d.cvel + ((size_t)w * m.nbody + m.dof_bodyid[i]) * 6, cdof + 6 * i, cd);
+        else
+          for (int k = 0; k < 6; ++k) cd[k] = d.cdof_dot[((size_t)w * nv + i) * 6 + k];
+        const V3 dang = ld3(cd), dlin = ld3(cd + 3);
+        if (a1) {
+          jp = jp + lin + cross(ang, s1.off);
+          jd = jd + dlin + cross(dang, s1.off) + cross(ang, s1.pvel);
+        }
+        if (a2) {
+          jp = jp - (lin + cross(ang, s2.off));
+          jd = jd - (dlin + cross(dang, s2.off) + cross(ang, s2.pvel));
+        }
+      }
+    }
+    jv[0] += jp.x * qv; jv[1] += jp.y * qv; jv[2] += jp.z * qv;
+    jdv[0] += jd.x * qv; jdv[1] += jd.y * qv; jdv[2] += jd.z * qv;
+    if (i < nvp) {
+      J[(size_t)r * nvp + i] = jp.x;
+      J[(size_t)(r + 1) * nvp + i] = jp.y;
+      J[(size_t)(r + 2) * nvp + i] = jp.z;
+    }
+  }
+  csum_n<G, 3>(jv);
+  csum_n<G, 3>(jdv);
+  if (lig < 3) {
+    const float* biw = bf(m.body_invweight0, m.body_invweight0_nb, w, 2 * m.nbody);
+    const float p = lig == 0 ? pos.x : (lig == 1 ? pos.y : pos.z);
+    const float vel = lig == 0 ? jv[0] : (lig == 1 ? jv[1] : jv[2]);
+    const float corr = lig == 0 ? jdv[0] : (lig == 1 ? jdv[1] : jdv[2]);
+    const EfcRowOut o = efc_row(m.disableflags, timestep, p, length(pos), biw[2 * s1.body] + biw[2 * s2.body],
+                                bf(m.eq_solref, m.eq_solref_nb, w, 2 * neq) + 2 * e, bf(m.eq_solimp, m.eq_solimp_nb, w, 5 * neq) + 5 * e, 0.0f, vel);
+    const size_t k = (size_t)w * d.njmax + r + lig;
+    d.efc_D[k] = o.D;
+    d.efc_aref[k] = o.aref - corr;
+    d.efc_pos[k] = o.pos;
+    d.efc_margin[k] = 0.0f;
+    d.efc_vel[k] = vel;
+    d.efc_frictionloss[k] = 0.0f;
+    d.efc_type[k] = CT_EQUALITY;
+    d.efc_id[k] = e;
+  }
+}
+
+// CONNECT (compile time): the equality section walks the equalities one after the other, every lane of the group on each -- a joint
+// coupling is one row, a connect three (connect_rows).  Only k_make_constraint of a model with connects is instantiated with it
+// (MjhModel.has_connect); the default is what k_mid and every other model run, and its code does not depend on the switch.
+template <int G, bool CONNECT = false>
 DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, const Blk& b, int stride_words = 0) {
   const int lig = threadIdx.x & (G - 1), gib = threadIdx.x / G;
   const int w = b.w0 + gib;
@@ -141,8 +236,65 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   pc.mark(0);
 
   int nefc = 0, ne = 0, nf = 0, nl = 0;
-  // ---- equality constraints: joint couplings (constraint.py:500-640); rows in equality-id order -------------
-  if (!(dsbl & DSBL_EQUALITY)) {
+  // ---- equality constraints: joint couplings (constraint.py:500-640) and, with CONNECT, connects; rows in equality-id order ----
+  if constexpr (CONNECT) {
+    if (!(dsbl & DSBL_EQUALITY)) {
+      const int neq = m.neq;
+      const float* qpos0 = bf(m.qpos0, m.qpos0_nb, w, m.nq);
+      for (int e = 0; e < neq; ++e) {
+        if (d.eq_active[(size_t)w * neq + e] == 0) continue;
+        if (m.eq_kind[e] == EQ_CONNECT) {
+          // a connect that does not fit writes none of its rows and is not counted (the rows behind it stay dense); the flag tells
+          if (nefc + 3 > njmax) {
+            if (lig == 0) atomicOr(d.overflow + w, OVF_NEFC);
+            continue;
+          }
+          connect_rows<G>(m, d, w, e, nefc, lig, timestep, cdof, qvel, scom, broot, bmask, J);
+          nefc += 3;
+          ne += 3;
+          continue;
+        }
+        // joint coupling: the row of the default instantiation below, its columns spread over the lanes
+        const int r = nefc;
+        if (r < njmax) {
+          const int j1 = m.eq_obj1id[e], j2 = m.eq_obj2id[e];
+          const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * neq) + 11 * e;
+          const int dof1 = m.jnt_dofadr[j1], qa1 = m.jnt_qposadr[j1];
+          int dof2 = -1;
+          float pos, vel, invweight, deriv = 0.0f;
+          if (j2 >= 0) {
+            dof2 = m.jnt_dofadr[j2];
+            const int qa2 = m.jnt_qposadr[j2];
+            const float dif = qpos[qa2] - qpos0[qa2];
+            const float rhs = data[0] + dif * (data[1] + dif * (data[2] + dif * (data[3] + dif * data[4])));
+            deriv = data[1] + dif * (2.0f * data[2] + dif * (3.0f * data[3] + dif * 4.0f * data[4]));
+            pos = qpos[qa1] - qpos0[qa1] - rhs;
+            vel = qvel[dof1] - qvel[dof2] * deriv;
+            invweight = invw[dof1] + invw[dof2];
+          } else {
+            pos = qpos[qa1] - qpos0[qa1] - data[0];
+            vel = qvel[dof1];
+            invweight = invw[dof1];
+          }
+          for (int c = lig; c < nvp; c += G) J[(size_t)r * nvp + c] = c == dof2 ? -deriv : (c == dof1 ? 1.0f : 0.0f);  // (dof2 last, as below)
+          if (lig == 0) {
+            EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invweight, bf(m.eq_solref, m.eq_solref_nb, w, 2 * neq) + 2 * e,
+                                  bf(m.eq_solimp, m.eq_solimp_nb, w, 5 * neq) + 5 * e, 0.0f, vel);
+            d.efc_D[eo + r] = o.D;
+            d.efc_aref[eo + r] = o.aref;
+            d.efc_pos[eo + r] = o.pos;
+            d.efc_margin[eo + r] = 0.0f;
+            d.efc_vel[eo + r] = vel;
+            d.efc_frictionloss[eo + r] = 0.0f;
+            d.efc_type[eo + r] = CT_EQUALITY;
+            d.efc_id[eo + r] = e;
+          }
+        }
+        ++nefc;
+        ++ne;
+      }
+    }
+  } else if (!(dsbl & DSBL_EQUALITY)) {
     const int neq = m.neq;
     const float* qpos0 = bf(m.qpos0, m.qpos0_nb, w, m.nq);
     for (int base = 0; base < neq; base += G) {
@@ -507,10 +659,10 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   pc.mark(5);
 }
 
-template <int G>
+template <int G, bool CONNECT = false>
 __global__ void __launch_bounds__(256) k_make_constraint(MjhModel m, MjhData d) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  make_constraint_body<G>(m, d, smem, blk_of_launch<G>());
+  make_constraint_body<G, CONNECT>(m, d, smem, blk_of_launch<G>());
 }
 
 
@@ -556,8 +708,8 @@ __global__ void __launch_bounds__(64) k_efc_j_sparse(MjhData d, int nv, int njma
 // M is block diagonal over kinematic trees, so the constraint problem of a world separates over the connected components of the graph
 // whose nodes are trees and whose edges are the rows touching two trees (a contact between bodies of two trees, a joint equality across
 // them) -- MuJoCo's constraint islands at tree granularity (reference island.py).  One 64-lane wavefront per world:
-//   1. tree(s) of every row from its type: equalities and limits through their joint, dof friction through its dof, contacts through
-//      the bodies of their geoms (a static body has no tree);
+//   1. tree(s) of every row from its type: joint equalities and limits through their joint, dof friction through its dof, contacts and
+//      connect equalities through their two bodies (a static or mocap body has no tree);
 //   2. connected components by min-label propagation over the coupling rows (LDS atomics, at most ntree sweeps);
 //   3. islands numbered by their smallest tree; their dofs (tree ranges concatenated in tree order) listed in ws_isl_dofmap with the
 //      inverse in ws_isl_dofinv, their rows grouped stably in ws_tree_rowmap; ws_isl_dofadr / ws_tree_rowadr delimit island k.
@@ -585,8 +737,15 @@ __global__ void __launch_bounds__(64) k_tree_rows(MjhModel m, MjhData d) {
     int t1 = 0, t2 = -1;
     if (type == CT_EQUALITY) {
       const int e = d.efc_id[eo + r], j1 = m.eq_obj1id[e], j2 = m.eq_obj2id[e];
-      t1 = m.dof_treeid[m.jnt_dofadr[j1]];
-      if (j2 >= 0) t2 = m.dof_treeid[m.jnt_dofadr[j2]];
+      if (m.has_connect && m.eq_kind[e] == EQ_CONNECT) {  // the trees of the two bodies, like a contact's (a static or mocap body has none)
+        const bool site = m.eq_kind[m.neq + e] == EQ_OBJ_SITE;
+        const int a = m.body_treeid[site ? m.site_bodyid[j1] : j1], b = m.body_treeid[site ? m.site_bodyid[j2] : j2];
+        t1 = a >= 0 ? a : (b >= 0 ? b : 0);
+        t2 = (a >= 0 && b >= 0) ? b : -1;
+      } else {
+        t1 = m.dof_treeid[m.jnt_dofadr[j1]];
+        if (j2 >= 0) t2 = m.dof_treeid[m.jnt_dofadr[j2]];
+      }
     } else if (type == CT_FRICTION_DOF) {
       t1 = m.dof_treeid[d.efc_id[eo + r]];
     } else if (type == CT_LIMIT_JOINT) {

@@ -273,9 +273,14 @@ static int launch_publish(const MjhModel* m, const MjhData* d, hipStream_t s) {
   hipLaunchKernelGGL(k_publish_contacts<32>, dim3((d->nworld + 256 / 32 - 1) / (256 / 32)), dim3(256), 0, s, *d, 1, m->nexplicit ? m->pair_solreffriction : nullptr);
   return MJH_OK;
 }
+// (a model with connect equalities, MjhModel.has_connect: the instantiation that carries their rows -- no other model launches it, and k_mid never)
 template <int G>
 static int launch_constraint_g(const MjhModel* m, const MjhData* d, hipStream_t s) {
   const ConLayout lay = con_layout(m->nv, d->njmax, d->concap, m->nbody, m->ngeom);
+  if (m->has_connect) {
+    if (!m->eq_kind) return fail(MJH_E_ARG, "Model.eq_kind missing (a model with connect equalities; INTEGRATION.md ABI v45)");
+    return launch_per_world(k_make_constraint<G, true>, "k_make_constraint: does not fit in LDS", G, 0, sizeof(float) * lay.total, d->nworld, s, *m, *d);
+  }
   return launch_per_world(k_make_constraint<G>, "k_make_constraint: does not fit in LDS", G, 0, sizeof(float) * lay.total, d->nworld, s, *m, *d);
 }
 static int launch_constraint(const MjhModel* m, const MjhData* d, hipStream_t s) { return lanes64(m) ? launch_constraint_g<64>(m, d, s) : launch_constraint_g<32>(m, d, s); }
@@ -767,6 +772,7 @@ static int check(const MjhModel* m, const MjhData* d) {
 
 // one wavefront per world (csrc/sleep.hpp k_sleep)
 static int launch_sleep(const MjhModel* m, const MjhData* d, int phase, hipStream_t s) {
+  if (m->has_connect) return fail(MJH_E_UNSUPPORTED, "k_sleep: connect equalities with sleeping (its wake and island passes index joints with an equality's ids)");
   const size_t lds = sizeof(int) * sleep_lds(m->ntree, m->nbody, m->nv, d->njmax, d->concap).total;
   if (lds > (size_t)kLdsPerCU) return fail(MJH_E_UNSUPPORTED, "k_sleep: the world's sleep tables do not fit in LDS");
   HIPCHK(set_lds(k_sleep, lds));
@@ -800,6 +806,8 @@ static int run_collide_constrain(const MjhModel* m, const MjhData* d, bool sleep
     d2.sleep_pass = 2;
     TRY(launch_collision(m, &d2, s));
   }
+  // connect rows carry -Jdot qvel of the CURRENT state: the velocity kinematics (cvel, cdof_dot) go in front of them
+  if (m->has_connect) { Scope sc(run, K_VEL); TRY(launch_vel(m, d, VEL_COMVEL, VEL_COMVEL, s)); }
   { Scope sc(run, K_CONSTRAINT); TRY(launch_constraint(m, d, s)); }
   if (sleep) { Scope sc(run, K_OTHER); TRY(launch_sleep(m, d, (int)SLP_POST_CONSTRAINT, s)); }
   return MJH_OK;
@@ -810,8 +818,8 @@ static int run_mid_unfused(const MjhModel* m, const MjhData* d, bool sleep, cons
   Scope sc(run, K_VEL);
   return launch_vel(m, d, VEL_COMVEL, VEL_ACCEL, run.s);
 }
-// forward / step as plain kernels: the profiling pass (so that the event pairs time one kernel at a time), MJH_PLAIN, and every model with
-// sleeping enabled (forward.py:345-349, 652-675, 1290-1324, 1341-1347)
+// forward / step as plain kernels: the profiling pass (so that the event pairs time one kernel at a time), MJH_PLAIN, every model with
+// sleeping enabled (forward.py:345-349, 652-675, 1290-1324, 1341-1347) and every model with connect equalities (k_mid does not carry them)
 static int run_unfused(const MjhModel* m, const MjhData* d, bool step, bool sleep, Run& run) {
   const hipStream_t s = run.s;
   if (sleep) {
@@ -928,7 +936,7 @@ static int run_stage_impl(const MjhModel* m, const MjhData* d, int stage, Run& r
     case MJH_STAGE_STEP: {
       const bool step = stage == MJH_STAGE_STEP;
       // MJH_PLAIN: developer knob, one plain kernel per stage, serial
-      if (m->sleep_enabled || KNOB_ONCE_FLAG("MJH_PLAIN") || (run.instr && run.instr->plain)) return run_unfused(m, d, step, m->sleep_enabled != 0, run);
+      if (m->sleep_enabled || m->has_connect || KNOB_ONCE_FLAG("MJH_PLAIN") || (run.instr && run.instr->plain)) return run_unfused(m, d, step, m->sleep_enabled != 0, run);
       // fused step: four launches on the caller's stream (see "composite launches" above), as plan_step decides
       StepPlan p = plan_step(m, d, stage, run.instr != nullptr);
       Streams* side = p.riders == RIDE_SIDE ? side_streams(run) : nullptr;

@@ -194,7 +194,7 @@ static inline int subtree_vel_wpb(int nbody) {
 
 // smooth.rne_postconstraint (smooth.py:1519-1826): cacc, cfrc_ext, cfrc_int with the constraint forces in.  cfrc_ext = applied Cartesian
 // forces + contact forces moved to the tree's centre of mass (spatial vectors: torque first); cacc from qacc down the tree; cfrc_int =
-// I cacc + v x* (I v) - cfrc_ext, summed towards the root (equality rows: joint equalities exert no cfrc_ext).
+// I cacc + v x* (I v) - cfrc_ext, summed towards the root (equality rows: joint equalities exert no cfrc_ext, connects do -- below).
 // One 32-lane group per world, one lane per body (round 3; was one thread per world): every lane scans the world's contacts in order and keeps
 // those of its body (deterministic sums); cacc of a body = the world's -g + the per-body terms of its ancestor chain; cfrc_int = the sum of the
 // bodies' own terms over the depth-first id range of the subtree.  LDS: 18 nbody floats per world.
@@ -249,6 +249,34 @@ __global__ void __launch_bounds__(256) k_rne_postconstraint(MjhModel m, MjhData 
         const V3 off = ld3(scom + 3 * m.body_rootid[b]) - ld3(rec + 1);
         if (b1 == b) add_force(force, torque, off, -1.0f);
         if (b2 == b) add_force(force, torque, off, 1.0f);
+      }
+      // connects (smooth.py:1570-1670): the three row forces act on body 1 at its anchor and, negated, on body 2 at its own; equality
+      // rows come first, in equality-id order: every lane walks them in that order
+      if (m.has_connect) {
+        const int ne = min(d.ne[w], d.njmax);
+        const int* efc_id = d.efc_id + (size_t)w * d.njmax;
+        for (int r = 0; r < ne;) {
+          const int e = efc_id[r];
+          if (m.eq_kind[e] != EQ_CONNECT) {  // (a joint coupling: one row, no Cartesian force)
+            ++r;
+            continue;
+          }
+          const bool site = m.eq_kind[m.neq + e] == EQ_OBJ_SITE;
+          const int o1 = m.eq_obj1id[e], o2 = m.eq_obj2id[e];
+          const int b1 = site ? m.site_bodyid[o1] : o1, b2 = site ? m.site_bodyid[o2] : o2;
+          if ((b1 == b || b2 == b) && r + 2 < d.njmax) {
+            const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * m.neq) + 11 * e;
+            const V3 force = ld3(efc_force + r);
+            for (int side = 0; side < 2; ++side) {
+              if ((side ? b2 : b1) != b) continue;
+              const int o = side ? o2 : o1;
+              const V3 p = site ? ld3(d.site_xpos + ((size_t)w * m.nsite + o) * 3)
+                                : ld3(d.xpos + ((size_t)w * nb + b) * 3) + mat_mul(d.xmat + ((size_t)w * nb + b) * 9, ld3(data + 3 * side));
+              add_force(force, V3{0, 0, 0}, ld3(scom + 3 * m.body_rootid[b]) - p, side ? -1.0f : 1.0f);
+            }
+          }
+          r += 3;
+        }
       }
     }
     for (int k = 0; k < 6; ++k) cext[6 * b + k] = c[k];

@@ -202,8 +202,17 @@ def _pair_types(mjm, pairs):
 def _check_supported(mjm, pairs):
   """Refuses what this engine does not compute (reference io.py:284-360): physics must not be dropped silently."""
   opt = mjm.opt
-  if int(getattr(mjm, "neq", 0)) > 0 and (np.asarray(mjm.eq_type) != types.EqType.JOINT).any():
-    raise NotImplementedError("only joint equality constraints are implemented")
+  if int(getattr(mjm, "neq", 0)) > 0:
+    # connect and joint equalities are built (csrc/constraint.hpp); weld, tendon and flex are refused, and so is a connect with sleeping
+    # enabled (csrc/sleep.hpp wakes and groups trees through the joints of an equality)
+    names = getattr(mjm, "eq_names", None)
+    who = lambda e: f"equality {e}" + (f" {names[e]!r}" if names is not None and len(names) > e and names[e] else "")
+    for e, t in enumerate(np.asarray(mjm.eq_type).reshape(-1)):
+      if int(t) not in (types.EqType.CONNECT, types.EqType.JOINT):
+        kind = types.EqType(int(t)).name.lower() if int(t) in tuple(types.EqType) else f"type {int(t)}"
+        raise NotImplementedError(f"{who(e)}: {kind} equality constraints are not implemented (connect and joint are)")
+      if int(t) == types.EqType.CONNECT and (int(opt.enableflags) & int(types.EnableBit.SLEEP)):
+        raise NotImplementedError(f"{who(e)}: a connect equality with sleeping enabled (EnableBit.SLEEP) is not implemented")
   for name in ("ntendon", "nflex", "nplugin"):
     if int(getattr(mjm, name, 0)) > 0:
       raise NotImplementedError(f"{name} > 0 is outside the hot-path scope of this engine")
@@ -489,7 +498,7 @@ _OPTIONAL_FIELDS = {
     sensor_type sensor_datatype sensor_objtype sensor_objid sensor_reftype sensor_refid sensor_dim sensor_adr sensor_cutoff
     sensor_intprm sensor_contact_adr sensor_collision_adr
     pair_dim pair_friction pair_solref pair_solreffriction pair_solimp pair_margin pair_gap site_bodyid site_pos site_quat
-    eq_obj1id eq_obj2id eq_solref eq_solimp eq_data""".split()),
+    eq_type eq_obj1id eq_obj2id eq_solref eq_solimp eq_data""".split()),
 }
 # sizes the Model takes from the length of one of its arrays (the host model's own counters are not consulted)
 _SIZE_FROM_ARRAY = {"nsensor": "sensor_type", "nmesh": "mesh_vertadr", "nmeshvert": "mesh_vert", "nmeshface": "mesh_face", "nmeshpoly": "mesh_polyvertnum",
@@ -617,6 +626,27 @@ def _contact_sensor_tables(host, nsensor_contact):
   return dict(sensor_intprm=np.ascontiguousarray(intprm, dtype=np.int32), sensor_contact_adr=np.concatenate([ids, np.full(n - len(ids), -1, dtype=np.int32)]))
 
 
+def _equality_tables(mjm, sizes):
+  """eq_type and eq_objtype [neq].  eq_objtype is optional in a host model: JOINT for a joint equality, BODY for a connect.  The ids of a
+  connect are checked here: csrc/constraint.hpp indexes the body / site tables with them."""
+  eq_type = _host_array(mjm, "eq_type", sizes)
+  if getattr(mjm, "eq_objtype", None) is None:
+    objtype = np.where(eq_type == types.EqType.JOINT, int(types.ObjType.JOINT), int(types.ObjType.BODY)).astype(np.int32)
+  else:
+    objtype = _arr(mjm.eq_objtype, np.int32).reshape(-1)
+  if objtype.shape != eq_type.shape:
+    raise ValueError(f"eq_objtype has {objtype.size} entries, expected neq = {eq_type.size}")
+  obj1 = _host_array(mjm, "eq_obj1id", sizes) if eq_type.size else np.zeros(0, dtype=np.int32)
+  obj2 = _host_array(mjm, "eq_obj2id", sizes) if eq_type.size else np.zeros(0, dtype=np.int32)
+  for e in np.flatnonzero(eq_type == types.EqType.CONNECT):
+    if int(objtype[e]) not in (types.ObjType.BODY, types.ObjType.SITE):
+      raise ValueError(f"equality {e}: a connect names bodies or sites, not objects of type {int(objtype[e])}")
+    n = int(mjm.nbody) if int(objtype[e]) == types.ObjType.BODY else int(getattr(mjm, "nsite", 0))
+    if not (0 <= int(obj1[e]) < n and 0 <= int(obj2[e]) < n):
+      raise ValueError(f"equality {e}: connect ids {int(obj1[e])}, {int(obj2[e])} are outside the model's {n} {'bodies' if int(objtype[e]) == types.ObjType.BODY else 'sites'}")
+  return dict(eq_type=eq_type, eq_objtype=objtype, eq_kind=np.stack([eq_type, objtype]).astype(np.int32))
+
+
 def _body_geoms(mjm, nbody):
   """body_geomnum / body_geomadr [nbody] from geom_bodyid (a body's geoms are contiguous, MuJoCo's order; adr -1 for a body without geoms):
   the same tables MuJoCo compiles, without asking the host model for them."""
@@ -693,6 +723,8 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   for name, value in facts.items():
     setattr(m, name, value)
   host.update(arrays)
+  host.update(_equality_tables(mjm, sizes))
+  m.has_connect = int((host["eq_type"] == types.EqType.CONNECT).any())
   for name in _MODEL_PTR_FIELDS:
     if name not in host:
       host[name] = _host_array(mjm, name, sizes)
@@ -730,6 +762,7 @@ def put_model(mjm, batch_sizes: Optional[dict] = None) -> types.Model:
   m.actuator_trnjnt = DeviceArray.from_numpy(host["actuator_trnjnt"]) if m.trn_general else m.actuator_trnid
   m.nxn_geom_pair_filtered = m.nxn_geom_pair
   m.sensor_interval = DeviceArray.from_numpy(host["sensor_interval"])
+  m.eq_type, m.eq_objtype = DeviceArray.from_numpy(host["eq_type"]), DeviceArray.from_numpy(host["eq_objtype"])  # (the library reads eq_kind)
   # (host copies of the buffer layout: make_data / reset_data write the buffers' initial state, the read / init functions check their arguments)
   m._history_buffers = history_buffers(*(host[k] for k in ("actuator_history", "actuator_historyadr", "sensor_history", "sensor_historyadr", "sensor_dim")))
   m._history_host = {k: host[k] for k in ("actuator_history", "sensor_history", "sensor_dim")}

@@ -537,6 +537,10 @@ class _Structure:
           if "class" not in c.attrib:
             c.set("class", main)
           self.section("equality").append(c)
+        elif eq.tag == "connect":  # (a loop closure must not vanish with the rest of the sub-model)
+          sites = {e.get("name") for e in src.iter("site") if e.get("name")}
+          if any(eq.get(k) in names["body"] for k in ("body1", "body2")) or any(eq.get(k) in sites for k in ("site1", "site2")):
+            raise NotImplementedError("<attach>: connect equalities of the attached model are not carried over; state them in the parent document")
     return body
 
   @staticmethod
@@ -1520,26 +1524,64 @@ def _compile(root, base_dir):
       na += 1
   m.na = na
 
-  # equality constraints: joint couplings only (constraint.py:500-640; Panda's finger coupling)
+  # equality constraints, in document order: joint couplings (constraint.py:500-640; Panda's finger coupling) and connects
+  # (constraint.py:156-496: a point of one body pinned to a point of another -- body1 [body2] anchor, or site1 site2)
   eqs = []
+  xkin = None  # body poses at qpos0, computed for the first body-form connect
+  site_names = [s_["name"] for s_ in sites]
+
+  def _eq_index(names, name, kind, tag):
+    if name not in names:
+      raise ValueError(f"<equality><{tag}>: unknown {kind} {name!r}")
+    return names.index(name)
+
   for child in (c for sec in root.findall("equality") for c in sec):
-    if child.tag != "joint":
-      raise NotImplementedError(f"<equality><{child.tag}> is outside the hot-path scope (only joint equalities are built)")
+    if child.tag not in ("joint", "connect"):
+      raise NotImplementedError(f"<equality><{child.tag}> is outside the hot-path scope (joint and connect equalities are built)")
     base, explicit = _resolve("equality", child, table, None)
     a = dict(base)
     a.update(explicit)
-    j2 = a.get("joint2")
     data = np.zeros(11)
-    data[:5] = _vec(a, "polycoef", [0.0, 1.0, 0.0, 0.0, 0.0])
-    eqs.append({"obj1": m.jnt_names.index(a["joint1"]), "obj2": m.jnt_names.index(j2) if j2 else -1,
+    if child.tag == "joint":
+      j2 = a.get("joint2")
+      data[:5] = _vec(a, "polycoef", [0.0, 1.0, 0.0, 0.0, 0.0])
+      etype, objtype = 2, 3  # mjEQ_JOINT, mjOBJ_JOINT
+      obj1 = _eq_index(m.jnt_names, a["joint1"], "joint", "joint")
+      obj2 = _eq_index(m.jnt_names, j2, "joint", "joint") if j2 else -1
+      for jid in (obj1, obj2):
+        if jid >= 0 and m.jnt_type[jid] not in (2, 3):
+          raise ValueError("joint equality needs slide or hinge joints")
+    else:
+      etype = 0  # mjEQ_CONNECT
+      body_form = "body1" in a or "body2" in a or "anchor" in a
+      site_form = "site1" in a or "site2" in a
+      if body_form == site_form:
+        raise ValueError("<equality><connect> takes either body1 [body2] anchor, or site1 site2" + (f" ({a['name']!r})" if a.get("name") else ""))
+      if site_form:
+        if "site1" not in a or "site2" not in a:
+          raise ValueError("<equality><connect>: the site form needs both site1 and site2")
+        objtype = 6  # mjOBJ_SITE
+        obj1, obj2 = (_eq_index(site_names, a[k], "site", "connect") for k in ("site1", "site2"))
+      else:
+        if "body1" not in a or "anchor" not in a:
+          raise ValueError("<equality><connect>: the body form needs body1 and anchor")
+        objtype = 1  # mjOBJ_BODY
+        obj1 = _eq_index(m.body_names, a["body1"], "body", "connect")
+        obj2 = _eq_index(m.body_names, a["body2"], "body", "connect") if a.get("body2") else 0  # (absent: the world)
+        # the anchor in body 1's frame and, the same world point at qpos0, in body 2's
+        if xkin is None:
+          xkin = _host_kinematics(m, m.qpos0)
+        xpos, xquat = xkin[0], xkin[1]
+        data[0:3] = _vec(a, "anchor", [0.0, 0.0, 0.0])
+        point = xpos[obj1] + nm.rot_vec_quat(data[0:3], xquat[obj1])
+        data[3:6] = nm.rot_vec_quat(point - xpos[obj2], nm.quat_conj(xquat[obj2]))
+    eqs.append({"name": a.get("name", ""), "type": etype, "objtype": objtype, "obj1": obj1, "obj2": obj2,
                 "active": _bool(a.get("active", "true")), "solref": _vec(a, "solref", [0.02, 1.0]),
                 "solimp": _vec(a, "solimp", [0.9, 0.95, 0.001, 0.5, 2.0]), "data": data})
-  for e in eqs:
-    for jid in (e["obj1"], e["obj2"]):
-      if jid >= 0 and m.jnt_type[jid] not in (2, 3):
-        raise ValueError("joint equality needs slide or hinge joints")
   m.neq = len(eqs)
-  m.eq_type = np.full(m.neq, 2, dtype=np.int32)  # mjEQ_JOINT
+  m.eq_names = [e["name"] for e in eqs]
+  m.eq_type = np.array([e["type"] for e in eqs], dtype=np.int32)  # mjtEq: 0 connect, 2 joint
+  m.eq_objtype = np.array([e["objtype"] for e in eqs], dtype=np.int32)  # mjtObj: 1 body, 6 site, 3 joint
   m.eq_obj1id = np.array([e["obj1"] for e in eqs], dtype=np.int32)
   m.eq_obj2id = np.array([e["obj2"] for e in eqs], dtype=np.int32)
   m.eq_active0 = np.array([int(e["active"]) for e in eqs], dtype=np.int32)

@@ -26,7 +26,8 @@ nv == 0: the subtree masses are computed, meaninertia is 1 and body_invweight0 i
 Out of scope:
   * actuator_acc0 and dampratio resolution: the loader refuses dampratio, and actuator_acc0 is not a device field;
   * cam_*0 and light_*0: ncam is 0;
-  * connect / weld eq_data: the engine has joint equalities only;
+  * connect eq_data: the second anchor (eq_data[3:6]) is computed by the loader at qpos0 and is per-world data of its own -- after moving
+    body frames or qpos0 on the device, write the anchors you mean (weld equalities are not built);
   * the host-only sleep tables dof_length and tree_sleep_policy;
   * set_length_range.
 """

@@ -81,6 +81,7 @@ class ObjType(enum.IntEnum):
   UNKNOWN = 0
   BODY = 1
   XBODY = 2
+  JOINT = 3
   GEOM = 5
   SITE = 6
   CAMERA = 7
@@ -507,6 +508,10 @@ class Model(_Dirty):
   momentT_adr: DeviceArray = _arr(('nv+1',), "int32")  # dof-major transpose: dof i owns momentT_act / momentT_ind [adr[i], adr[i + 1])
   momentT_act: DeviceArray = _arr_own(('nJmom',), "int32")
   momentT_ind: DeviceArray = _arr_own(('nJmom',), "int32")
+  has_connect: int = 0  # 1: some equality is a connect (forward / step run the unfused stage order, velocity kinematics before the rows)
+  eq_type: DeviceArray = _arr(('neq',), "int32")  # EqType: CONNECT or JOINT (put_model refuses the others)
+  eq_objtype: DeviceArray = _arr(('neq',), "int32")  # ObjType of obj1id / obj2id: BODY or SITE (connect), JOINT
+  eq_kind: DeviceArray = _arr((2, 'neq'), "int32")  # what the library reads: eq_type and eq_objtype as the two rows of one table
   eq_obj1id: DeviceArray = _arr(('neq',), "int32")
   eq_obj2id: DeviceArray = _arr(('neq',), "int32")
   eq_solref: DeviceArray = _arr(('*', 'neq', 2), "float32")
