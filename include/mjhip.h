@@ -383,6 +383,16 @@ int mjh_forward(const MjhModel* m, const MjhData* d, void* stream);
 int mjh_solve_m(const MjhModel* m, const MjhData* d, float* x, const float* y, void* stream);
 /* res = M vec (support.mul_m support.py:218) */
 int mjh_mul_m(const MjhModel* m, const MjhData* d, float* res, const float* vec, void* stream);
+/* Inverse dynamics (reference inverse.py; csrc/inverse.hpp; an addition within ABI v45: no struct changed).
+ * mjh_inv_constraint (inverse.inv_constraint): ONE launch that evaluates the constraint forces at the acceleration qacc [nworld, nv] on the rows
+ * make_constraint left -- Data.efc_force, efc_state, qfrc_constraint = J' force -- and, unless qfrc_inverse is NULL, writes
+ * qfrc_inverse [nworld, nv] = M qacc + qfrc_bias - qfrc_passive - qfrc_constraint.
+ * mjh_inverse (inverse.inverse): fwd_position, fwd_velocity, the position / velocity sensors, mjh_inv_constraint at Data.qacc, the acceleration
+ * sensors -- through the launches of mjh_stage, on `stream`, without synchronising or allocating.  With EnableBit.INVDISCRETE (Euler integrator
+ * only) Data.qacc is the discrete acceleration (qvel' - qvel) / h and everything is evaluated at M^-1 (M + h diag(dof_damping)) qacc, kept in
+ * scratch [2, nworld, nv] (may be NULL otherwise); Data.qacc is never written.  Sleeping models are refused. */
+int mjh_inv_constraint(const MjhModel* m, const MjhData* d, const float* qacc, float* qfrc_inverse, void* stream);
+int mjh_inverse(const MjhModel* m, const MjhData* d, float* qfrc_inverse, float* scratch, void* stream);
 /* CSR copy of the dense efc.J in the reference's sparse layout (types.py:2021-2070: J_rownnz / J_rowadr [nworld, njmax], J_colind / J
  * [nworld, njmax_nnz]; the reference stores efc.J this way for nv > 32, io.py:1804-1808).  Entries = the numerically non-zero values of
  * each row (a subset of the reference's structural pattern); rows whose entries do not fit njmax_nnz are truncated and

@@ -75,34 +75,7 @@ __host__ __device__ inline ConLayout con_layout(int nv, int njmax, int ncap, int
   return p;
 }
 
-// sums of N values over the G lanes of a group, the result in every lane (VALU only: DPP row shifts, then the row sums are combined)
-template <int G, int N>
-DEV void csum_n(float (&v)[N]) {
-  static_assert(G == 16 || G == 32 || G == 64, "lane groups of 16, 32 or 64");
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x111, 0xf, 0xf>(v[i]);  // row_shr:1
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x112, 0xf, 0xf>(v[i]);  // row_shr:2
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x114, 0xf, 0xf>(v[i]);  // row_shr:4
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x118, 0xf, 0xf>(v[i]);  // row_shr:8: lane 15 of every 16-lane row holds the row's sum
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    if (G == 16) {
-      v[i] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x15F, 0xf, 0xf, true));  // row_newbcast:15
-    } else if (G == 32) {
-      const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
-      const float lo = __int_as_float(__builtin_amdgcn_update_dpp(0, (int)sw[0], 0x15F, 0xf, 0xf, true));
-      const float hi = __int_as_float(__builtin_amdgcn_update_dpp(0, (int)sw[1], 0x15F, 0xf, 0xf, true));
-      v[i] = lo + hi;
-    } else {
-      float x = dpp_add_f<0x142, 0xa, 0xf>(v[i]);  // row_bcast:15 into rows 1 and 3
-      x = dpp_add_f<0x143, 0xc, 0xf>(x);           // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's sum
-      v[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-    }
-  }
-}
+// (csum_n<G, N> -- sums of N values over the lanes of a group, DPP, fixed order -- lives in dev_common.hpp: k_inverse uses it too)
 
 // ---- connect equalities (constraint.py:156-496) ---------------------------------------------------------------------------------------
 // A connect pins a point of body 1 to a point of body 2: three rows, pos = p1 - p2, J = jacp(b1, p1) - jacp(b2, p2), and the reference

@@ -33,7 +33,7 @@ enum { DSBL_CONSTRAINT = 1 << 0, DSBL_EQUALITY = 1 << 1, DSBL_FRICTIONLOSS = 1 <
        DSBL_REFSAFE = 1 << 12, DSBL_SENSOR = 1 << 13, DSBL_EULERDAMP = 1 << 15, DSBL_NATIVECCD = 1 << 17, DSBL_MULTICCD = 1 << 19 };
 enum { SOL_PGS = 0, SOL_CG = 1, SOL_NEWTON = 2 };
 enum { CONE_PYRAMIDAL = 0, CONE_ELLIPTIC = 1 };
-enum { ENBL_ENERGY = 1 << 1, ENBL_SLEEP = 1 << 5 };
+enum { ENBL_ENERGY = 1 << 1, ENBL_INVDISCRETE = 1 << 3, ENBL_SLEEP = 1 << 5 };
 enum { ISL_WIDE = 1, ISL_MANYROWS = 2 };
 enum { ISL_LIST_MANYROWS = 0, ISL_LIST_WIDE = 1, ISL_LIST_GENERIC = 2 };  // Data.ws_isl_list / ws_isl_count classes  // Data.ws_isl_flags: a world holds an island of 33..64 dofs / of <= 32 dofs and > 64 rows
 #define CON_STRIDE 32  /* words per contact record in d.ws_contact (layout: collide.hpp) */
@@ -72,6 +72,34 @@ DEV float gsum(float v) {
 #pragma unroll
   for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, G);
   return v;
+}
+// sums of N values over the G lanes of a group, the result in every lane (VALU only: DPP row shifts, then the row sums are combined)
+template <int G, int N>
+DEV void csum_n(float (&v)[N]) {
+  static_assert(G == 16 || G == 32 || G == 64, "lane groups of 16, 32 or 64");
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x111, 0xf, 0xf>(v[i]);  // row_shr:1
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x112, 0xf, 0xf>(v[i]);  // row_shr:2
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x114, 0xf, 0xf>(v[i]);  // row_shr:4
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = dpp_add_f<0x118, 0xf, 0xf>(v[i]);  // row_shr:8: lane 15 of every 16-lane row holds the row's sum
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if (G == 16) {
+      v[i] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x15F, 0xf, 0xf, true));  // row_newbcast:15
+    } else if (G == 32) {
+      const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
+      const float lo = __int_as_float(__builtin_amdgcn_update_dpp(0, (int)sw[0], 0x15F, 0xf, 0xf, true));
+      const float hi = __int_as_float(__builtin_amdgcn_update_dpp(0, (int)sw[1], 0x15F, 0xf, 0xf, true));
+      v[i] = lo + hi;
+    } else {
+      float x = dpp_add_f<0x142, 0xa, 0xf>(v[i]);  // row_bcast:15 into rows 1 and 3
+      x = dpp_add_f<0x143, 0xc, 0xf>(x);           // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's sum
+      v[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+    }
+  }
 }
 template <int G>
 DEV float gmax(float v) {

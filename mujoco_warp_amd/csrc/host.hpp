@@ -15,6 +15,7 @@
 //   history_tu.hip (k_history_ctrl, k_history_sensor, k_history_read, k_history_init and the entry points mjh_history_read / mjh_history_init:
 //   actuator and sensor delays, only for models with MjhModel.nhistory > 0),
 //   reset_tu.hip (k_reset and its entry point mjh_reset: reset_data / reset_data_keyframe on the device; never launched by a step),
+//   inverse_tu.hip (k_inverse: inverse dynamics, the launch of mjh_inverse / mjh_inv_constraint; never launched by a step),
 //   build_id.hip (the source hash, no kernels)
 // Device code is header-only and fully inlined per kernel, so no relocatable device code is needed.
 #pragma once
@@ -185,3 +186,8 @@ int launch_history_ctrl(const MjhModel* m, const MjhData* d, int insert, hipStre
 int launch_history_sensor(const MjhModel* m, const MjhData* d, int stage, int insert, hipStream_t s);
 // reset of the worlds `r` selects (reset.hpp, reset_tu.hip): mjh_reset, and the first node of the graph of mjh_graph_create_reset
 int launch_reset(const MjhModel* m, const MjhData* d, const MjhReset* r, hipStream_t s);
+// inverse dynamics (inverse.hpp, inverse_tu.hip): efc_force / efc_state / qfrc_constraint at the acceleration `qacc` [nworld, nv] and, unless
+// qfrc_inverse is null, qfrc_inverse = M qacc + qfrc_bias - qfrc_passive - qfrc_constraint; G: the caller's lane choice for the model
+// (16 / 32 / 64).  launch_inverse_eulerdamp (invdiscrete, Euler): buf = h dof_damping Data.qacc (add == 0), buf += Data.qacc (add == 1)
+int launch_inverse(const MjhModel* m, const MjhData* d, const float* qacc, float* qfrc_inverse, int G, hipStream_t s);
+int launch_inverse_eulerdamp(const MjhModel* m, const MjhData* d, float* buf, int add, hipStream_t s);

@@ -1062,6 +1062,52 @@ int mjh_mul_m(const MjhModel* m, const MjhData* d, float* res, const float* vec,
   return launch_solve_m(m, d, res, vec, 1, (hipStream_t)stream);
 }
 
+// ---- inverse dynamics (csrc/inverse.hpp; the kernel and its launchers are inverse_tu.hip's) ----------------------------------------------
+// lanes per world of k_inverse: what k_mid / k_make_constraint choose for the model
+static int inverse_lanes(const MjhModel* m) { return lanes16(m) ? 16 : (lanes64(m) ? 64 : 32); }
+static const char INVERSE_SLEEP[] = "inverse dynamics with sleeping enabled (the two-pass collision and the asleep-tree shortcuts are not defined for it)";
+int mjh_inv_constraint(const MjhModel* m, const MjhData* d, const float* qacc, float* qfrc_inverse, void* stream) {
+  TRY(check(m, d));
+  if (m->sleep_enabled) return fail(MJH_E_UNSUPPORTED, "%s", INVERSE_SLEEP);
+  TRY(launch_inverse(m, d, qacc, qfrc_inverse, inverse_lanes(m), (hipStream_t)stream));
+  HIPCHK(hipGetLastError());
+  return MJH_OK;
+}
+// inverse.inverse (inverse.py:148-182) through the stage launchers of mjh_stage: fwd_position (a model with connects: com_vel in front of its
+// rows), fwd_velocity, the position / velocity sensors (one launch here, behind both stages), invdiscrete: the continuous-time acceleration,
+// k_inverse, the acceleration sensors.  Data.qacc is only read: the continuous-time acceleration lives in `scratch`, where k_inverse and the
+// acceleration sensors read it.
+int mjh_inverse(const MjhModel* m, const MjhData* d, float* qfrc_inverse, float* scratch, void* stream) {
+  TRY(check(m, d));
+  if (!qfrc_inverse) return fail(MJH_E_ARG, "mjh_inverse: null qfrc_inverse");
+  if (m->sleep_enabled) return fail(MJH_E_UNSUPPORTED, "%s", INVERSE_SLEEP);
+  const bool discrete = (m->enableflags & ENBL_INVDISCRETE) != 0;
+  if (discrete && m->integrator != INT_EULER)
+    return fail(MJH_E_UNSUPPORTED, "discrete inverse dynamics (invdiscrete) with the %s integrator: only Euler is implemented",
+                m->integrator == INT_RK4 ? "RK4" : (m->integrator == INT_IMPLICITFAST ? "implicitfast" : "implicit"));
+  Run run(stream);
+  const hipStream_t s = run.s;
+  TRY(run_stage(m, d, MJH_STAGE_FWD_POSITION, run));
+  TRY(run_stage(m, d, MJH_STAGE_FWD_VELOCITY, run));
+  TRY(run_stage(m, d, MJH_STAGE_SENSOR_POSVEL, run));
+  MjhData dq = *d;  // what k_inverse and the acceleration sensors read as qacc
+  if (discrete && !(m->disableflags & (DSBL_EULERDAMP | DSBL_DAMPER)) && m->nv > 0) {
+    // discrete_acc (inverse.py:79-119), Euler: qacc_c = M^-1 (M + h diag(dof_damping)) qacc = qacc + M^-1 (h dof_damping qacc)
+    if (!scratch) return fail(MJH_E_ARG, "mjh_inverse: invdiscrete needs scratch [2, nworld, nv]");
+    float* rhs = scratch;
+    float* qacc_c = scratch + (size_t)d->nworld * m->nv;
+    Scope sc(run, K_OTHER);
+    TRY(launch_inverse_eulerdamp(m, d, rhs, 0, s));
+    TRY(launch_solve_m(m, d, qacc_c, rhs, 0, s));
+    TRY(launch_inverse_eulerdamp(m, d, qacc_c, 1, s));
+    dq.qacc = qacc_c;
+  }
+  { Scope sc(run, K_SOLVE); TRY(launch_inverse(m, &dq, dq.qacc, qfrc_inverse, inverse_lanes(m), s)); }
+  TRY(run_stage(m, &dq, MJH_STAGE_SENSOR_ACC, run));
+  HIPCHK(hipGetLastError());
+  return MJH_OK;
+}
+
 int mjh_qld_dense(const MjhModel* m, const MjhData* d, float* qld_dense, int stride, void* stream) {
   TRY(check(m, d));
   if (!qld_dense || stride < 0) return fail(MJH_E_ARG, "mjh_qld_dense: null output");

@@ -245,7 +245,7 @@ def _check_supported(mjm, pairs):
       raise NotImplementedError(f"{name} (polynomial stiffness / damping) is not implemented.")
   if float(getattr(opt, "density", 0.0)) != 0.0 or float(getattr(opt, "viscosity", 0.0)) != 0.0:
     raise NotImplementedError("fluid forces (option density / viscosity, passive.py _fluid_force) are not implemented.")
-  unsupported_enable = int(opt.enableflags) & int(types.EnableBit.OVERRIDE | types.EnableBit.FWDINV | types.EnableBit.INVDISCRETE)
+  unsupported_enable = int(opt.enableflags) & int(types.EnableBit.OVERRIDE | types.EnableBit.FWDINV)
   if unsupported_enable:
     raise NotImplementedError(f"enable flags {types.EnableBit(unsupported_enable)!r} are not implemented.")
   # sleeping (reference io.py:356-360): Newton only; active when islands are not disabled (forward.py:345)
@@ -957,6 +957,8 @@ def _alloc_data(m: types.Model, nworld, nconmax, njmax, naconmax, mjd=None, nvma
   for name in _DATA_PTR_FIELDS:
     shape, dtype, _ = _DATA_ARRAYS[name]
     _set_data_field(d, name, DeviceArray.zeros(types.eval_shape(shape, sizes), dtype=dtype))
+  d.qfrc_inverse = DeviceArray.zeros((nworld, m.nv), dtype="float32")  # (inverse() passes it to mjh_inverse as an argument: MjhData has no member for it)
+  d.ws_inverse = DeviceArray.zeros((2, nworld, m.nv), dtype="float32")  # (its invdiscrete scratch, here so that no call of inverse() allocates)
   for name in ("nworld", "naconmax", "njmax", "njmax_pad", "nv_pad", "nsleepworld", "npgsworld", "nimpworld", "nccdworld", "nccdword", "concap"):
     setattr(d, name, sizes[name])
   d.nconmax = nconmax
@@ -1084,7 +1086,7 @@ def get_data_into(result, mjm, d: types.Data, world_id: int = 0):
   for name in ("qpos", "qvel", "act", "ctrl", "qacc_warmstart", "qfrc_applied", "xfrc_applied", "mocap_pos", "mocap_quat", "qacc", "xpos", "xquat",
                "xmat", "xipos", "ximat", "xanchor", "xaxis", "geom_xpos", "geom_xmat", "subtree_com", "cinert", "cdof", "crb",
                "qLD", "qLDiagInv", "cvel", "cdof_dot", "qfrc_bias", "qfrc_passive", "qfrc_spring", "qfrc_damper",
-               "qfrc_actuator", "qfrc_smooth", "qacc_smooth", "qfrc_constraint", "actuator_force", "actuator_length",
+               "qfrc_actuator", "qfrc_smooth", "qacc_smooth", "qfrc_constraint", "qfrc_inverse", "actuator_force", "actuator_length",
                "actuator_velocity", "cacc", "cfrc_int"):
     arr = getattr(d, name).numpy()[w]
     cur = getattr(result, name, None)

@@ -713,6 +713,8 @@ class Data(_Dirty):
   qacc_smooth: DeviceArray = _arr(('nworld', 'nv'), "float32")
   qacc: DeviceArray = _arr(('nworld', 'nv'), "float32")
   qfrc_constraint: DeviceArray = _arr(('nworld', 'nv'), "float32")
+  qfrc_inverse: DeviceArray = _arr(('nworld', 'nv'), "float32")  # inverse(): the force that produces qacc (reference types.py Data.qfrc_inverse); not in MjhData
+  ws_inverse: DeviceArray = _arr((2, 'nworld', 'nv'), "float32")  # inverse() with invdiscrete: mjh_inverse's scratch (an argument; not in MjhData)
   solver_niter: DeviceArray = _arr(('nworld',), "int32")
   ne: DeviceArray = _arr(('nworld',), "int32")
   nf: DeviceArray = _arr(('nworld',), "int32")
