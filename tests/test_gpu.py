@@ -77,9 +77,12 @@ def _check_contacts_and_rows(s, d, mjm, w=-1, dist_atol=2e-7):
       assert relerr(getattr(d.contact, a).numpy()[sl].reshape(ncon, -1), getattr(s, b)[:ncon].reshape(ncon, -1)) <= 1e-6
     np.testing.assert_array_equal(d.contact.efc_address.numpy()[sl], s.con_efc_address[:ncon, : d.nmaxpyramid])
   nefc = int(d.nefc.numpy()[ww])
-  assert (nefc, int(d.nf.numpy()[ww]), int(d.nl.numpy()[ww])) == (s.nefc, s.nf, s.nl)
+  assert (nefc, int(d.ne.numpy()[ww]), int(d.nf.numpy()[ww]), int(d.nl.numpy()[ww])) == (s.nefc, s.ne, s.nf, s.nl)
   n = min(nefc, d.njmax)
   if n:
+    # efc.id: the equality / dof / joint of the row; contact rows carry the public contact id (this world's slice starts at ws_conadr)
+    ids, contact_row = d.efc.id.numpy()[ww, :n], s.efc_type[:n] >= 5
+    np.testing.assert_array_equal(ids - adr * contact_row, s.efc_id[:n])
     assert relerr(d.efc.J.numpy()[ww, :n, : mjm.nv], s.efc_J[:n]) <= SMOOTH
     assert (d.efc.J.numpy()[ww, :n, mjm.nv :] == 0).all()
     np.testing.assert_array_equal(d.efc.type.numpy()[ww, :n], s.efc_type[:n])
