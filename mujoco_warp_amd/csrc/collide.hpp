@@ -1077,13 +1077,12 @@ DEV PairParams contact_params(const MjhModel& m, int w, int g1, int g2, int pid 
     p.gap = m.pair_gap[pid];
     return p;
   }
-  const int ng = m.ngeom;
-  const float* gm = bf(m.geom_margin, m.geom_margin_nb, w, ng);
-  const float* gg = bf(m.geom_gap, m.geom_gap_nb, w, ng);
-  const float* gsm = bf(m.geom_solmix, m.geom_solmix_nb, w, ng);
-  const float* gfr = bf(m.geom_friction, m.geom_friction_nb, w, 3 * ng);
-  const float* gsr = bf(m.geom_solref, m.geom_solref_nb, w, 2 * ng);
-  const float* gsi = bf(m.geom_solimp, m.geom_solimp_nb, w, 5 * ng);
+  const float* gm = BF(m, geom_margin, w);
+  const float* gg = BF(m, geom_gap, w);
+  const float* gsm = BF(m, geom_solmix, w);
+  const float* gfr = BF(m, geom_friction, w);
+  const float* gsr = BF(m, geom_solref, w);
+  const float* gsi = BF(m, geom_solimp, w);
   p.margin = gm[g1] + gm[g2];
   p.gap = gg[g1] + gg[g2];
   const float s1 = gsm[g1], s2 = gsm[g2];
@@ -1267,10 +1266,10 @@ DEV void collision_body(const MjhModel& m, const MjhData& d, float* smem, const 
     gcopy<G>(S, d.geom_xpos + (size_t)w * 3 * ng, 3 * ng, lig);
     gcopy<G>(S + 3 * ng, d.geom_xmat + (size_t)w * 9 * ng, 9 * ng, lig);
   }
-  const float* rbound = tbl ? tbl : bf(m.geom_rbound, m.geom_rbound_nb, w, ng);
-  const float* gmargin = tbl ? tbl + ng : bf(m.geom_margin, m.geom_margin_nb, w, ng);
-  const float* ggap = tbl ? tbl + 2 * ng : bf(m.geom_gap, m.geom_gap_nb, w, ng);
-  const float* gsize = bf(m.geom_size, m.geom_size_nb, w, 3 * ng);
+  const float* rbound = tbl ? tbl : BF(m, geom_rbound, w);
+  const float* gmargin = tbl ? tbl + ng : BF(m, geom_margin, w);
+  const float* ggap = tbl ? tbl + 2 * ng : BF(m, geom_gap, w);
+  const float* gsize = BF(m, geom_size, w);
   gsync();
   if (MODE == 1 && m.broadphase != 0) {  // (the NXN tests ran in k_broad_mask)
     for (int g = lig; g < ng; g += G) {
@@ -1288,7 +1287,7 @@ DEV void collision_body(const MjhModel& m, const MjhData& d, float* smem, const 
   // broadphase.  Plane / bounding-sphere filters live in both instantiations; AABB / OBB filters and the sweep-and-prune
   // candidate generator only in the HEAVY one (the light k_mid sits exactly at its 4-waves-per-SIMD register budget).
   const int filt = HEAVY ? m.broadphase_filter : 3;
-  const float* gaabb = HEAVY ? (tbl ? tbl + 3 * ng : bf(m.geom_aabb, m.geom_aabb_nb, w, 6 * ng)) : nullptr;
+  const float* gaabb = HEAVY ? (tbl ? tbl + 3 * ng : BF(m, geom_aabb, w)) : nullptr;
   unsigned* sapmark = nullptr;
   int ncand = 0, nbroad = 0;
   if (HEAVY && MODE == 0 && pre) {  // k_ccd_broad's list (the convex results are keyed by the rank in exactly this list)
@@ -1567,7 +1566,7 @@ DEV void collision_body(const MjhModel& m, const MjhData& d, float* smem, const 
   float* ccd_scratch = (HFC && ccd_world && m.nhfield > 0) ? ccd_world + CL.hf + (lig & (CCD_LANES - 1)) : nullptr;  // height-field prisms only
   const float* ccd_cache = ccd_world ? ccd_world + CL.cache : nullptr;  // results of k_ccd_gjk / k_ccd_epa, one entry per convex candidate
   const int hf0 = ccd_words(max(m.ccd_iterations, m.epa_iterations), 0);  // first word of the lane's height-field result table
-  const float ccd_tol = HEAVY ? bf(m.opt_ccd_tolerance, m.opt_ccd_tolerance_nb, w, 1)[0] : 0.0f;
+  const float ccd_tol = HEAVY ? BF(m, opt_ccd_tolerance, w)[0] : 0.0f;
   const int ccd_it = min(m.ccd_iterations, CCD_MAX_ITER), epa_it = min(m.epa_iterations, CCD_MAX_ITER);
   const int ccd_cache0 = ccd_poly_words(max(m.ccd_iterations, m.epa_iterations));  // first word of the lane's contact cache
   const bool box_ccd = !(m.disableflags & DSBL_NATIVECCD);  // box-box: CCD + multi-contact unless the flag asks for mjc_BoxBox
@@ -1846,13 +1845,13 @@ __global__ void __launch_bounds__(256) k_broad_mask(MjhModel m, MjhData d) {
     if (d.sleep_pass == 2 && !d.ws_sleep_flag[w]) continue;  // (uniform over the workgroup; k_ccd_broad skips these worlds too)
     const float* gxpos = d.geom_xpos + (size_t)w * 3 * ng;
     const float* gxmat = d.geom_xmat + (size_t)w * 9 * ng;
-    const float* gaabb = bf(m.geom_aabb, m.geom_aabb_nb, w, 6 * ng);
+    const float* gaabb = BF(m, geom_aabb, w);
     __syncthreads();  // the previous world's readers are done
     bool nz = false;  // any margin or gap in this world's tables
     {
-      const float* rb = bf(m.geom_rbound, m.geom_rbound_nb, w, ng);
-      const float* mg = bf(m.geom_margin, m.geom_margin_nb, w, ng);
-      const float* ga = bf(m.geom_gap, m.geom_gap_nb, w, ng);
+      const float* rb = BF(m, geom_rbound, w);
+      const float* mg = BF(m, geom_margin, w);
+      const float* ga = BF(m, geom_gap, w);
       for (int g = tid; g < ng; g += 256) {
         const V3 x = ld3(gxpos + 3 * g);
         *reinterpret_cast<float4*>(gx4 + 4 * g) = make_float4(x.x, x.y, x.z, rb[g]);
@@ -2163,9 +2162,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MJH_GJ
     }
     const int ng = m.ngeom;
     const int pid = m.nexplicit ? m.nxn_pairid[p] : -1;
-    const float* gmargin = bf(m.geom_margin, m.geom_margin_nb, w, ng);
-    const float* ggap = bf(m.geom_gap, m.geom_gap_nb, w, ng);
-    const float* gsize = bf(m.geom_size, m.geom_size_nb, w, 3 * ng);
+    const float* gmargin = BF(m, geom_margin, w);
+    const float* ggap = BF(m, geom_gap, w);
+    const float* gsize = BF(m, geom_size, w);
     const float margin = pid >= 0 ? m.pair_margin[pid] : gmargin[g1] + gmargin[g2];
     const float gap = pid >= 0 ? m.pair_gap[pid] : ggap[g1] + ggap[g2];
     const float* gxpos = d.geom_xpos + (size_t)w * 3 * ng;
@@ -2176,7 +2175,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MJH_GJ
     if (t2 == G_MESH) { me2 = m.geom_dataid[g2]; mv2 = m.mesh_vert + 3 * m.mesh_vertadr[me2]; mn2 = m.mesh_vertnum[me2]; }
     float* cache = d.ws_ccd + (size_t)w * CL.world_stride + CL.cache + (size_t)slot * CCD_CACHE_WORDS;
     int nem = 0;
-    const float ccd_tol = bf(m.opt_ccd_tolerance, m.opt_ccd_tolerance_nb, w, 1)[0];
+    const float ccd_tol = BF(m, opt_ccd_tolerance, w)[0];
 #ifdef MJH_DBG_GJK_CLOCK
     if (lig == 0) atomicAdd(cnt + 5, (int)((__builtin_amdgcn_s_memtime() - kt0_) >> 10));  // pair set-up
     kt0_ = __builtin_amdgcn_s_memtime();
@@ -2271,9 +2270,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MJH_EP
   }
   const int ng = m.ngeom;
   const int pid = m.nexplicit ? m.nxn_pairid[p] : -1;
-  const float* gmargin = bf(m.geom_margin, m.geom_margin_nb, w, ng);
-  const float* ggap = bf(m.geom_gap, m.geom_gap_nb, w, ng);
-  const float* gsize = bf(m.geom_size, m.geom_size_nb, w, 3 * ng);
+  const float* gmargin = BF(m, geom_margin, w);
+  const float* ggap = BF(m, geom_gap, w);
+  const float* gsize = BF(m, geom_size, w);
   const float margin = pid >= 0 ? m.pair_margin[pid] : gmargin[g1] + gmargin[g2];
   const float gap = pid >= 0 ? m.pair_gap[pid] : ggap[g1] + ggap[g2];
   const float* gxpos = d.geom_xpos + (size_t)w * 3 * ng;
@@ -2285,7 +2284,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MJH_EP
   float* cache = d.ws_ccd + (size_t)w * CL.world_stride + CL.cache + (size_t)slot * CCD_CACHE_WORDS;
   float* mcws = nullptr;  // (the multi-contact recovery's lists live in the group's LDS)
   int nem = 0, overflow = 0;
-  const float ccd_tol = bf(m.opt_ccd_tolerance, m.opt_ccd_tolerance_nb, w, 1)[0];
+  const float ccd_tol = BF(m, opt_ccd_tolerance, w)[0];
   convex_epa_group<G>(ccd_tol, min(m.epa_iterations, CCD_MAX_ITER), t1, t2, ld3(gxpos + 3 * g1), gxmat + 9 * g1, ld3(gsize + 3 * g1), ld3(gxpos + 3 * g2), gxmat + 9 * g2, ld3(gsize + 3 * g2),
                       margin, gap, poly, overflow, [&](int k, float dist, V3 pos, V3 fa, V3 fb, V3 fc) { ccd_cache_store(cache, nem, k, dist, pos, fa, fb, fc, lig == 0); },
                       mv1, mn1, mv2, mn2, m, me1, me2, res, idx1, idx2, lig, mcws);

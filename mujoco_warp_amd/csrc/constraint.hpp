@@ -105,7 +105,7 @@ template <int G>
 DEV void connect_rows(const MjhModel& m, const MjhData& d, int w, int e, int r, int lig, float timestep, const float* cdof, const float* qvel,
                       const float* scom, const int* broot, const unsigned* bmask, float* J) {
   const int nv = m.nv, nvp = d.nv_pad, neq = m.neq, nw = (nv + 31) / 32;
-  const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * neq) + 11 * e;
+  const float* data = BF(m, eq_data, w) + 11 * e;
   const bool site = m.eq_kind[neq + e] == EQ_OBJ_SITE;
   const ConnectSide s1 = connect_side(m, d, w, site, m.eq_obj1id[e], ld3(data), scom, broot);
   const ConnectSide s2 = connect_side(m, d, w, site, m.eq_obj2id[e], ld3(data + 3), scom, broot);
@@ -151,12 +151,12 @@ DEV void connect_rows(const MjhModel& m, const MjhData& d, int w, int e, int r, 
   csum_n<G, 3>(jv);
   csum_n<G, 3>(jdv);
   if (lig < 3) {
-    const float* biw = bf(m.body_invweight0, m.body_invweight0_nb, w, 2 * m.nbody);
+    const float* biw = BF(m, body_invweight0, w);
     const float p = lig == 0 ? pos.x : (lig == 1 ? pos.y : pos.z);
     const float vel = lig == 0 ? jv[0] : (lig == 1 ? jv[1] : jv[2]);
     const float corr = lig == 0 ? jdv[0] : (lig == 1 ? jdv[1] : jdv[2]);
     const EfcRowOut o = efc_row(m.disableflags, timestep, p, length(pos), biw[2 * s1.body] + biw[2 * s2.body],
-                                bf(m.eq_solref, m.eq_solref_nb, w, 2 * neq) + 2 * e, bf(m.eq_solimp, m.eq_solimp_nb, w, 5 * neq) + 5 * e, 0.0f, vel);
+                                BF(m, eq_solref, w) + 2 * e, BF(m, eq_solimp, w) + 5 * e, 0.0f, vel);
     const size_t k = (size_t)w * d.njmax + r + lig;
     d.efc_D[k] = o.D;
     d.efc_aref[k] = o.aref - corr;
@@ -202,9 +202,9 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   gcopyi<G>(gbody, m.geom_bodyid, m.ngeom, lig);
   gcopyi<G>(broot, m.body_rootid, nbody, lig);
   for (int i = lig; i < nbody * ((nv + 31) / 32); i += G) bmask[i] = m.body_dofmask[i];
-  const float timestep = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float timestep = BF(m, opt_timestep, w)[0];
   const float* qpos = d.qpos + (size_t)w * m.nq;
-  const float* invw = bf(m.dof_invweight0, m.dof_invweight0_nb, w, nv);
+  const float* invw = BF(m, dof_invweight0, w);
   gsync();
   pc.mark(0);
 
@@ -213,7 +213,7 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   if constexpr (CONNECT) {
     if (!(dsbl & DSBL_EQUALITY)) {
       const int neq = m.neq;
-      const float* qpos0 = bf(m.qpos0, m.qpos0_nb, w, m.nq);
+      const float* qpos0 = BF(m, qpos0, w);
       for (int e = 0; e < neq; ++e) {
         if (d.eq_active[(size_t)w * neq + e] == 0) continue;
         if (m.eq_kind[e] == EQ_CONNECT) {
@@ -231,7 +231,7 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
         const int r = nefc;
         if (r < njmax) {
           const int j1 = m.eq_obj1id[e], j2 = m.eq_obj2id[e];
-          const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * neq) + 11 * e;
+          const float* data = BF(m, eq_data, w) + 11 * e;
           const int dof1 = m.jnt_dofadr[j1], qa1 = m.jnt_qposadr[j1];
           int dof2 = -1;
           float pos, vel, invweight, deriv = 0.0f;
@@ -251,8 +251,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
           }
           for (int c = lig; c < nvp; c += G) J[(size_t)r * nvp + c] = c == dof2 ? -deriv : (c == dof1 ? 1.0f : 0.0f);  // (dof2 last, as below)
           if (lig == 0) {
-            EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invweight, bf(m.eq_solref, m.eq_solref_nb, w, 2 * neq) + 2 * e,
-                                  bf(m.eq_solimp, m.eq_solimp_nb, w, 5 * neq) + 5 * e, 0.0f, vel);
+            EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invweight, BF(m, eq_solref, w) + 2 * e,
+                                  BF(m, eq_solimp, w) + 5 * e, 0.0f, vel);
             d.efc_D[eo + r] = o.D;
             d.efc_aref[eo + r] = o.aref;
             d.efc_pos[eo + r] = o.pos;
@@ -269,7 +269,7 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
     }
   } else if (!(dsbl & DSBL_EQUALITY)) {
     const int neq = m.neq;
-    const float* qpos0 = bf(m.qpos0, m.qpos0_nb, w, m.nq);
+    const float* qpos0 = BF(m, qpos0, w);
     for (int base = 0; base < neq; base += G) {
       const int e = base + lig;
       const bool act = e < neq && d.eq_active[(size_t)w * neq + e] != 0;
@@ -277,7 +277,7 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
       const int r = nefc + grank<G>(act, lig, tot);
       if (act && r < njmax) {
         const int j1 = m.eq_obj1id[e], j2 = m.eq_obj2id[e];
-        const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * neq) + 11 * e;
+        const float* data = BF(m, eq_data, w) + 11 * e;
         const int dof1 = m.jnt_dofadr[j1], qa1 = m.jnt_qposadr[j1];
         for (int c = 0; c < nvp; ++c) J[(size_t)r * nvp + c] = 0.0f;
         J[(size_t)r * nvp + dof1] = 1.0f;
@@ -296,8 +296,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
           vel = qvel[dof1];
           invweight = invw[dof1];
         }
-        EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invweight, bf(m.eq_solref, m.eq_solref_nb, w, 2 * neq) + 2 * e,
-                              bf(m.eq_solimp, m.eq_solimp_nb, w, 5 * neq) + 5 * e, 0.0f, vel);
+        EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invweight, BF(m, eq_solref, w) + 2 * e,
+                              BF(m, eq_solimp, w) + 5 * e, 0.0f, vel);
         d.efc_D[eo + r] = o.D;
         d.efc_aref[eo + r] = o.aref;
         d.efc_pos[eo + r] = o.pos;
@@ -314,7 +314,7 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   const int nrow_equality = nefc;
   // ---- dof friction loss (constraint.py:1766-1865) ---------------------------------------------------------
   if (!(dsbl & DSBL_FRICTIONLOSS)) {
-    const float* fl = bf(m.dof_frictionloss, m.dof_frictionloss_nb, w, nv);
+    const float* fl = BF(m, dof_frictionloss, w);
     for (int base = 0; base < nv; base += G) {
       const int i = base + lig;
       const bool act = i < nv && fl[i] > 0.0f;
@@ -324,8 +324,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
         rowdof[r] = i;
         rowval[r] = 1.0f;
         const float vel = qvel[i];
-        EfcRowOut o = efc_row(dsbl, timestep, 0.0f, 0.0f, invw[i], bf(m.dof_solref, m.dof_solref_nb, w, 2 * nv) + 2 * i,
-                              bf(m.dof_solimp, m.dof_solimp_nb, w, 5 * nv) + 5 * i, 0.0f, vel);
+        EfcRowOut o = efc_row(dsbl, timestep, 0.0f, 0.0f, invw[i], BF(m, dof_solref, w) + 2 * i,
+                              BF(m, dof_solimp, w) + 5 * i, 0.0f, vel);
         d.efc_D[eo + r] = o.D;
         d.efc_aref[eo + r] = o.aref;
         d.efc_pos[eo + r] = o.pos;
@@ -342,8 +342,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   // ---- joint limits (constraint.py:1991-2240) ---------------------------------------------------------------
   int nball = 0;
   if (!(dsbl & DSBL_LIMIT)) {
-    const float* jrange = bf(m.jnt_range, m.jnt_range_nb, w, 2 * njnt);
-    const float* jmargin = bf(m.jnt_margin, m.jnt_margin_nb, w, njnt);
+    const float* jrange = BF(m, jnt_range, w);
+    const float* jmargin = BF(m, jnt_margin, w);
     for (int base = 0; base < njnt; base += G) {
       const int j = base + lig;
       bool act = false;
@@ -381,8 +381,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
           rowval[r] = jval;
           vel = jval * qvel[dof];
         }
-        EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invw[dof], bf(m.jnt_solref, m.jnt_solref_nb, w, 2 * njnt) + 2 * j,
-                              bf(m.jnt_solimp, m.jnt_solimp_nb, w, 5 * njnt) + 5 * j, margin, vel);
+        EfcRowOut o = efc_row(dsbl, timestep, pos, pos, invw[dof], BF(m, jnt_solref, w) + 2 * j,
+                              BF(m, jnt_solimp, w) + 5 * j, margin, vel);
         d.efc_D[eo + r] = o.D;
         d.efc_aref[eo + r] = o.aref;
         d.efc_pos[eo + r] = o.pos;
@@ -476,8 +476,8 @@ DEV void make_constraint_body(const MjhModel& m, const MjhData& d, float* smem, 
   //      (nothing of J is read back); solref / solimp come from `crec`.
   // (An earlier design note here described a pre-pass that rewrote compact records in active order; it was never what the code does.)
   const int nw = (nv + 31) / 32;
-  const float impr2 = bf(m.opt_impratio_invsqrt, m.opt_impratio_invsqrt_nb, w, 1)[0];
-  const float* biw = bf(m.body_invweight0, m.body_invweight0_nb, w, 2 * nbody);
+  const float impr2 = BF(m, opt_impratio_invsqrt, w)[0];
+  const float* biw = BF(m, body_invweight0, w);
   int a = 0;
   for (int wbase = 0; wbase < ncon && a < nactive; wbase += CON_WINDOW) {
     const int wend = min(wbase + CON_WINDOW, ncon);

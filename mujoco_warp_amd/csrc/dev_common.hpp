@@ -130,8 +130,70 @@ DEV int grank(bool p, int lig, int& total) {
   return __popcll(bits & ((1ull << lig) - 1ull));
 }
 
-// batched ("*") model field row: ptr + (w % nb) * stride   (reference types.py:1535-1808)
+// batched ("*") model field row: ptr + (w % nb) * stride   (reference types.py:1535-1808).  Called by BF below and by nothing else.
 DEV const float* bf(const float* p, int nb, int w, int stride) { return p + (size_t)(nb > 1 ? (w % nb) : 0) * stride; }
+// The floats of one world's row of every batched field of MjhModel (the fields with a companion <field>_nb in mjhip.h), over m only: the
+// product of the shape types.py declares behind '*'.  One entry per field, and the only statement of a row size on the C side
+// (tests/test_io_schema.py holds the table to the schema).
+#define MJH_ROW_opt_timestep(m) (1)
+#define MJH_ROW_opt_tolerance(m) (1)
+#define MJH_ROW_opt_ls_tolerance(m) (1)
+#define MJH_ROW_opt_gravity(m) (3)
+#define MJH_ROW_opt_impratio_invsqrt(m) (1)
+#define MJH_ROW_opt_ccd_tolerance(m) (1)
+#define MJH_ROW_opt_magnetic(m) (3)
+#define MJH_ROW_stat_meaninertia(m) (1)
+#define MJH_ROW_qpos0(m) ((m).nq)
+#define MJH_ROW_qpos_spring(m) ((m).nq)
+#define MJH_ROW_body_pos(m) (3 * (m).nbody)
+#define MJH_ROW_body_quat(m) (4 * (m).nbody)
+#define MJH_ROW_body_ipos(m) (3 * (m).nbody)
+#define MJH_ROW_body_iquat(m) (4 * (m).nbody)
+#define MJH_ROW_body_mass(m) ((m).nbody)
+#define MJH_ROW_body_subtreemass(m) ((m).nbody)
+#define MJH_ROW_body_inertia(m) (3 * (m).nbody)
+#define MJH_ROW_body_invweight0(m) (2 * (m).nbody)
+#define MJH_ROW_body_gravcomp(m) ((m).nbody)
+#define MJH_ROW_jnt_solref(m) (2 * (m).njnt)
+#define MJH_ROW_jnt_solimp(m) (5 * (m).njnt)
+#define MJH_ROW_jnt_pos(m) (3 * (m).njnt)
+#define MJH_ROW_jnt_axis(m) (3 * (m).njnt)
+#define MJH_ROW_jnt_stiffness(m) ((m).njnt)
+#define MJH_ROW_jnt_range(m) (2 * (m).njnt)
+#define MJH_ROW_jnt_margin(m) ((m).njnt)
+#define MJH_ROW_jnt_actfrcrange(m) (2 * (m).njnt)
+#define MJH_ROW_dof_solref(m) (2 * (m).nv)
+#define MJH_ROW_dof_solimp(m) (5 * (m).nv)
+#define MJH_ROW_dof_frictionloss(m) ((m).nv)
+#define MJH_ROW_dof_armature(m) ((m).nv)
+#define MJH_ROW_dof_damping(m) ((m).nv)
+#define MJH_ROW_dof_invweight0(m) ((m).nv)
+#define MJH_ROW_geom_solmix(m) ((m).ngeom)
+#define MJH_ROW_geom_solref(m) (2 * (m).ngeom)
+#define MJH_ROW_geom_solimp(m) (5 * (m).ngeom)
+#define MJH_ROW_geom_size(m) (3 * (m).ngeom)
+#define MJH_ROW_geom_rbound(m) ((m).ngeom)
+#define MJH_ROW_geom_aabb(m) (6 * (m).ngeom)
+#define MJH_ROW_geom_pos(m) (3 * (m).ngeom)
+#define MJH_ROW_geom_quat(m) (4 * (m).ngeom)
+#define MJH_ROW_geom_friction(m) (3 * (m).ngeom)
+#define MJH_ROW_geom_margin(m) ((m).ngeom)
+#define MJH_ROW_geom_gap(m) ((m).ngeom)
+#define MJH_ROW_site_pos(m) (3 * (m).nsite)
+#define MJH_ROW_site_quat(m) (4 * (m).nsite)
+#define MJH_ROW_actuator_dynprm(m) (10 * (m).nu)
+#define MJH_ROW_actuator_gainprm(m) (10 * (m).nu)
+#define MJH_ROW_actuator_biasprm(m) (10 * (m).nu)
+#define MJH_ROW_actuator_ctrlrange(m) (2 * (m).nu)
+#define MJH_ROW_actuator_forcerange(m) (2 * (m).nu)
+#define MJH_ROW_actuator_actrange(m) (2 * (m).nu)
+#define MJH_ROW_actuator_gear(m) (6 * (m).nu)
+#define MJH_ROW_eq_solref(m) (2 * (m).neq)
+#define MJH_ROW_eq_solimp(m) (5 * (m).neq)
+#define MJH_ROW_eq_data(m) (11 * (m).neq)
+// world w's row of a batched field, by the field's bare name: BF(m, dof_damping, w).  The one way a kernel reads such a field; the staged-table
+// fills (smooth.hpp, collide.hpp) read row 0 directly, each behind a guard that lists <field>_nb <= 1 for every field it stages.
+#define BF(m, field, w) bf((m).field, (m).field##_nb, (w), MJH_ROW_##field(m))
 
 // ---- small vector math ----------------------------------------------------------------------------
 struct V3 {

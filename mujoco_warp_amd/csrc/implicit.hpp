@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(64) k_implicit_solve(MjhModel m, MjhData d) {
   float *cdof = S + lay.cdof, *cdot = S + lay.cdot, *cvel = S + lay.cvel, *cinert = S + lay.cinert, *qvel = S + lay.qvel, *rhs = S + lay.rhs,
         *A = S + lay.A, *ws = S + lay.ws;
   const int AS = lay.AS;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   const size_t vo = (size_t)w * nv;
   const int dsbl = m.disableflags;
   gcopy<G>(cdof, d.cdof + 6 * vo, 6 * nv, lig);
@@ -63,8 +63,8 @@ __global__ void __launch_bounds__(64) k_implicit_solve(MjhModel m, MjhData d) {
   // ---- A = M + h damping - h d(qfrc_actuator)/dv (the implicitfast matrix, dense) -------------------------------------------------
   {
     const float* Mg = d.M + (size_t)w * nC;
-    const float* damp = bf(m.dof_damping, m.dof_damping_nb, w, nv);
-    const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
+    const float* damp = BF(m, dof_damping, w);
+    const float* gear = BF(m, actuator_gear, w);
     for (int i = lig; i < nv; i += G) {
       const int start = m.M_rowadr[i], n = m.M_rownnz[i];
       for (int a = 0; a < n; ++a) {
@@ -81,14 +81,14 @@ __global__ void __launch_bounds__(64) k_implicit_solve(MjhModel m, MjhData d) {
       if (!(dsbl & DSBL_ACTUATION))
         for (int u = 0; u < nu; ++u) {
           if (m.jnt_dofadr[m.actuator_trnid[2 * u]] != i) continue;
-          const float bias_vel = m.actuator_biastype[u] == 1 ? bf(m.actuator_biasprm, m.actuator_biasprm_nb, w, 10 * nu)[10 * u + 2] : 0.0f;
-          const float gain_vel = m.actuator_gaintype[u] == 1 ? bf(m.actuator_gainprm, m.actuator_gainprm_nb, w, 10 * nu)[10 * u + 2] : 0.0f;
+          const float bias_vel = m.actuator_biastype[u] == 1 ? BF(m, actuator_biasprm, w)[10 * u + 2] : 0.0f;
+          const float gain_vel = m.actuator_gaintype[u] == 1 ? BF(m, actuator_gainprm, w)[10 * u + 2] : 0.0f;
           float ctrl = d.ctrl[(size_t)w * nu + u];  // the RAW control (derivative.py:159-161)
           if (m.actuator_dyntype[u] != 0) ctrl = d.act[(size_t)w * m.na + m.actuator_actadr[u]];
           const float dv = bias_vel + gain_vel * ctrl;
           if (dv == 0.0f) continue;
           if (m.actuator_forcelimited[u]) {
-            const float* fr = bf(m.actuator_forcerange, m.actuator_forcerange_nb, w, 2 * nu) + 2 * u;
+            const float* fr = BF(m, actuator_forcerange, w) + 2 * u;
             const float f = d.actuator_force[(size_t)w * nu + u];
             if (f <= fr[0] || f >= fr[1]) continue;
           }

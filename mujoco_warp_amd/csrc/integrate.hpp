@@ -36,9 +36,9 @@ DEV void integrate_body(const MjhModel& m, const MjhData& d, int mode, float* sm
   float* S = smem + mstruct_ints(nv, nC) + (size_t)gib * lay.total;
   float *L = S + lay.L, *dinv = S + lay.dinv, *x = S + lay.x, *qvel = S + lay.qvel;
   const int dsbl = m.disableflags;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   const size_t vo = (size_t)w * nv;
-  const float* damp = bf(m.dof_damping, m.dof_damping_nb, w, nv);
+  const float* damp = BF(m, dof_damping, w);
   PhaseClock pc(6, lig);
 
   // does the velocity update need an implicit solve?  (mode 2: the fully implicit integrator solved its system in k_implicit_solve)
@@ -84,13 +84,13 @@ DEV void integrate_body(const MjhModel& m, const MjhData& d, int mode, float* sm
     float act = d.act[a];
     const float act_dot = d.act_dot[a];
     if (dyn == 3) {
-      const float tau = fmaxf(MJ_MINVAL, bf(m.actuator_dynprm, m.actuator_dynprm_nb, w, 10 * nu)[10 * u]);
+      const float tau = fmaxf(MJ_MINVAL, BF(m, actuator_dynprm, w)[10 * u]);
       act = act + act_dot * tau * (1.0f - expf(-h / tau));
     } else {
       act = act + act_dot * h;
     }
     if (m.actuator_actlimited[u]) {
-      const float* ar = bf(m.actuator_actrange, m.actuator_actrange_nb, w, 2 * nu) + 2 * u;
+      const float* ar = BF(m, actuator_actrange, w) + 2 * u;
       act = clampf(act, ar[0], ar[1]);
     }
     d.act[a] = act;
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256) k_rk4(MjhModel m, MjhData d, int stage, f
   float* vel = smem + (size_t)gib * (nv + 1);  // the velocity the position update integrates
   float* rk = d.ws_rk + (size_t)w * (nq + 3 * nv + 2 * na);
   float *qpos0 = rk, *qvel0 = rk + nq, *qvel_rk = qvel0 + nv, *qacc_rk = qvel_rk + nv, *act0 = qacc_rk + nv, *actdot_rk = act0 + na;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   const bool last = stage == 3;
   const float dt = last ? h : a * h;
   const size_t vo = (size_t)w * nv;
@@ -172,13 +172,13 @@ __global__ void __launch_bounds__(256) k_rk4(MjhModel m, MjhData d, int stage, f
     const float rate = last ? sd : cd;
     float act;
     if (dyn == 3) {
-      const float tau = fmaxf(MJ_MINVAL, bf(m.actuator_dynprm, m.actuator_dynprm_nb, w, 10 * nu)[10 * u]);
+      const float tau = fmaxf(MJ_MINVAL, BF(m, actuator_dynprm, w)[10 * u]);
       act = a0 + rate * tau * (1.0f - expf(-dt / tau));
     } else {
       act = a0 + rate * dt;
     }
     if (m.actuator_actlimited[u]) {
-      const float* ar = bf(m.actuator_actrange, m.actuator_actrange_nb, w, 2 * nu) + 2 * u;
+      const float* ar = BF(m, actuator_actrange, w) + 2 * u;
       act = clampf(act, ar[0], ar[1]);
     }
     d.act[ga] = act;
@@ -234,11 +234,11 @@ DEV void ctrl_noise_elem(const MjhModel& m, const MjhData& d, const float* cente
   const int nu = m.nu;
   if (idx >= d.nworld * nu) return;
   const int w = idx / nu, a = idx - w * nu;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   const float rate = expf(-h / noise_rate);
   const float scale = noise_std * sqrtf(1.0f - rate * rate);
   float midpoint = 0.0f, halfrange = 1.0f;
-  const float* cr = bf(m.actuator_ctrlrange, m.actuator_ctrlrange_nb, w, 2 * nu) + 2 * a;
+  const float* cr = BF(m, actuator_ctrlrange, w) + 2 * a;
   const bool lim = m.actuator_ctrllimited[a];
   if (lim) {
     midpoint = 0.5f * (cr[1] + cr[0]);

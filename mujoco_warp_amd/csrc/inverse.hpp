@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) k_inverse(MjhModel m, MjhData d, const fl
   const int ne = d.ne[w], nf = d.nf[w], nfric = ne + nf, ncon0 = nfric + d.nl[w];  // (equality | friction loss | limit | contact rows)
   const bool ell = m.cone == CONE_ELLIPTIC && d.nmaxpyramid > 1;
   const bool has_fl = nf > 0;
-  const float impr = ell ? bf(m.opt_impratio_invsqrt, m.opt_impratio_invsqrt_nb, w, 1)[0] : 1.0f;
+  const float impr = ell ? BF(m, opt_impratio_invsqrt, w)[0] : 1.0f;
   const float* Jg = d.efc_J + (size_t)w * d.njmax_pad * nvp;
   // the contact of an elliptic row: first row of its contact, rows of the contact that exist (0: not a row of a multi-row elliptic contact)
   auto ell_row = [&](int r, int& r0, int& dim) __attribute__((always_inline)) {
@@ -179,5 +179,5 @@ __global__ void k_inverse_eulerdamp(MjhModel m, MjhData d, float* buf, int add) 
   if (idx >= d.nworld * nv) return;
   const int w = idx / nv, i = idx - w * nv;
   if (add) buf[idx] += d.qacc[idx];
-  else buf[idx] = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0] * bf(m.dof_damping, m.dof_damping_nb, w, nv)[i] * d.qacc[idx];
+  else buf[idx] = BF(m, opt_timestep, w)[0] * BF(m, dof_damping, w)[i] * d.qacc[idx];
 }

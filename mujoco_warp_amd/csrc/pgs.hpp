@@ -199,8 +199,8 @@ DEV void pgs_body(const MjhModel& m, const MjhData& d, float* smem, const Blk& b
   gsync();
 
   // ---- sweeps ------------------------------------------------------------------------------------------------------
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
   const float rscale = 1.0f / (meaninertia * (float)max(nv, 1));
   const int maxiter = m.iterations;
   int niter = 0;

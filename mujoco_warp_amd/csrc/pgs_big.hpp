@@ -466,7 +466,7 @@ DEV void pgs_big_body(const MjhModel& m, const MjhData& d, float* smem, int w) {
         int r0 = r;
         while (info[r0] == 7) --r0;
         const int dim = info[r0] - 8;
-        const float mu = d.ws_contact[((size_t)w * d.concap + (d.ws_efc_con[eo + r0] >> 4)) * CON_STRIDE + 14] * bf(m.opt_impratio_invsqrt, m.opt_impratio_invsqrt_nb, w, 1)[0];
+        const float mu = d.ws_contact[((size_t)w * d.concap + (d.ws_efc_con[eo + r0] >> 4)) * CON_STRIDE + 14] * BF(m, opt_impratio_invsqrt, w)[0];
         float tt = 0.0f;
         for (int j = 1; j < dim; ++j) tt += (xs[r0 + j] * rmu[r0 + j]) * (xs[r0 + j] * rmu[r0 + j]);
         const float N = xs[r0] * mu, T = tt <= 0.0f ? 0.0f : sqrtf(tt);
@@ -614,8 +614,8 @@ DEV void pgs_big_body(const MjhModel& m, const MjhData& d, float* smem, int w) {
   int* colc = reinterpret_cast<int*>(Bc + ctl[2]);
 
   // ---- sweeps ---------------------------------------------------------------------------------------------------------------------
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float rscale = 1.0f / (bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0] * (float)max(nv, 1));
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float rscale = 1.0f / (BF(m, stat_meaninertia, w)[0] * (float)max(nv, 1));
   const int maxiter = m.iterations;
   int niter = 0;
   // J_r . q over the lanes' dofs (partial; reduce with gsumg / gsumg_n)

@@ -254,7 +254,7 @@ DEV bool ray_box_overlap(V3 centre, V3 half, V3 lpnt, V3 lvec) {
 // The reference culls with a box of geom_size about the geom origin; the mesh frame here is the principal frame at the centre of mass, whose
 // bounding box is not centred, so the cull takes the geom's own geom_aabb (centre and half sizes)
 DEV bool ray_mesh_cull(const MjhModel& m, int w, int g, V3 pos, const float* mat, V3 pnt, V3 vec) {  // true: the ray misses the mesh's box
-  const float* ab = bf(m.geom_aabb, m.geom_aabb_nb, w, 6 * m.ngeom) + 6 * g;
+  const float* ab = BF(m, geom_aabb, w) + 6 * g;
   return !ray_box_overlap(ld3(ab), ld3(ab + 3), matT_mul(mat, pnt - pos), matT_mul(mat, vec));
 }
 DEV void ray_mesh(const MjhModel& m, int g, V3 pos, const float* mat, V3 pnt, V3 vec, int lane, int nlane, RayHit& h) {
@@ -380,7 +380,7 @@ DEV float ray_world(const MjhModel& m, const MjhData& d, int w, V3 pnt, V3 vec, 
     if (ray_eliminate(m, g, gg, flg_static, bodyexclude)) continue;
     V3 n;
     const float dist = ray_geom(m.geom_type[g], ld3(d.geom_xpos + ((size_t)w * m.ngeom + g) * 3), d.geom_xmat + ((size_t)w * m.ngeom + g) * 9,
-                                ld3(bf(m.geom_size, m.geom_size_nb, w, 3 * m.ngeom) + 3 * g), pnt, vec, n);
+                                ld3(BF(m, geom_size, w) + 3 * g), pnt, vec, n);
     if (dist >= 0.0f && dist < best) {
       best = dist;
       geomid = g;
@@ -421,7 +421,7 @@ DEV bool ray_geom_first(const MjhModel& m, const MjhData& d, int w, int g, V3 pn
   if (type == G_MESH) return !ray_mesh_cull(m, w, g, pos, mat, pnt, vec);
   if (type == G_HFIELD) return true;
   V3 n;
-  const float x = ray_geom(type, pos, mat, ld3(bf(m.geom_size, m.geom_size_nb, w, 3 * m.ngeom) + 3 * g), pnt, vec, n);
+  const float x = ray_geom(type, pos, mat, ld3(BF(m, geom_size, w) + 3 * g), pnt, vec, n);
   ray_hit_take(h, x, g, 0, n);
   return false;
 }

@@ -126,14 +126,14 @@ __global__ void __launch_bounds__(64 * RENDER_TILES_PER_BLOCK) k_render(MjhModel
       type = m.geom_type[g];
       pos = ld3(d.geom_xpos + ((size_t)w * m.ngeom + g) * 3);
       shared = type == G_MESH || type == G_HFIELD;
-      keep = type == G_PLANE || type == G_HFIELD || no_cone || render_cone_sphere(o, a, ct, st, pos, bf(m.geom_rbound, m.geom_rbound_nb, w, m.ngeom)[g]);
+      keep = type == G_PLANE || type == G_HFIELD || no_cone || render_cone_sphere(o, a, ct, st, pos, BF(m, geom_rbound, w)[g]);
     }
     const unsigned long long kp = __ballot(keep && !shared), ks = __ballot(keep && shared), below = (1ull << lane) - 1ull;
     const int nprim = __popcll(kp), nshared = __popcll(ks);
     if (keep) {
       float* e = list + RENDER_ENTRY * (shared ? 63 - __popcll(ks & below) : __popcll(kp & below));
       const float* mat = d.geom_xmat + ((size_t)w * m.ngeom + g) * 9;
-      const float* size = bf(m.geom_size, m.geom_size_nb, w, 3 * m.ngeom) + 3 * g;
+      const float* size = BF(m, geom_size, w) + 3 * g;
       e[0] = __int_as_float(type);
       e[1] = __int_as_float(g);
       st3(e + 2, pos);

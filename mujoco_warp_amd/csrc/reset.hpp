@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256) k_reset(MjhModel m, MjhData d, MjhReset r
 
   // ---- the state ----
   {
-    const float* src = key >= 0 ? r.key_qpos + (size_t)key * m.nq : m.qpos0 + (size_t)(w % m.qpos0_nb) * m.nq;
+    const float* src = key >= 0 ? r.key_qpos + (size_t)key * m.nq : BF(m, qpos0, w);
     for (int i = lane; i < m.nq; i += 64) d.qpos[sw * m.nq + i] = src[i];
   }
   for (int i = lane; i < m.nv; i += 64) {
@@ -67,15 +67,16 @@ __global__ void __launch_bounds__(256) k_reset(MjhModel m, MjhData d, MjhReset r
   // ---- mocap poses: the model's, then the keyframe's ----
   if (m.nmocap > 0) {
     const bool from_key = key >= 0 && key < r.nkey_mocap;
+    const float *body_pos = BF(m, body_pos, w), *body_quat = BF(m, body_quat, w);
     for (int i = lane; i < 3 * m.nmocap; i += 64) {
       const int k = i / 3, c = i - 3 * k;
       d.mocap_pos[sw * 3 * m.nmocap + i] = from_key ? r.key_mpos[(size_t)key * 3 * m.nmocap + i]
-                                                    : m.body_pos[((size_t)(w % m.body_pos_nb) * m.nbody + r.mocap_bodyid[k]) * 3 + c];
+                                                    : body_pos[r.mocap_bodyid[k] * 3 + c];
     }
     for (int i = lane; i < 4 * m.nmocap; i += 64) {
       const int k = i >> 2, c = i & 3;
       d.mocap_quat[sw * 4 * m.nmocap + i] = from_key ? r.key_mquat[(size_t)key * 4 * m.nmocap + i]
-                                                     : m.body_quat[((size_t)(w % m.body_quat_nb) * m.nbody + r.mocap_bodyid[k]) * 4 + c];
+                                                     : body_quat[r.mocap_bodyid[k] * 4 + c];
     }
   }
 
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(256) k_reset(MjhModel m, MjhData d, MjhReset r
   // ---- the delay buffers in their initial state at the new time (actuator buffers, then sensor buffers: history.hpp) ----
   if (m.nhistory > 0) {
     float* row = d.history + sw * m.nhistory;
-    const float timestep = m.opt_timestep[w % m.opt_timestep_nb];
+    const float timestep = BF(m, opt_timestep, w)[0];
     for (int u = 0; u < m.nu; ++u) {
       const int n = m.actuator_history[2 * u];
       if (n > 0) reset_history_buffer(row + m.actuator_historyadr[u], n, 1, time, timestep, lane);

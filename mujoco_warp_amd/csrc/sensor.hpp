@@ -47,10 +47,10 @@ DEV SensFrame sens_frame(const MjhModel& m, const MjhData& d, int w, int objtype
 // sensor.py:342-374 _get_quat
 DEV Q4 sens_quat(const MjhModel& m, const MjhData& d, int w, int objtype, int id) {
   const float* xquat = d.xquat + (size_t)w * m.nbody * 4;
-  if (objtype == OBJ_BODY) return mul_quat(ld4(xquat + 4 * id), ld4(bf(m.body_iquat, m.body_iquat_nb, w, 4 * m.nbody) + 4 * id));
+  if (objtype == OBJ_BODY) return mul_quat(ld4(xquat + 4 * id), ld4(BF(m, body_iquat, w) + 4 * id));
   if (objtype == OBJ_XBODY) return ld4(xquat + 4 * id);
-  if (objtype == OBJ_GEOM) return mul_quat(ld4(xquat + 4 * m.geom_bodyid[id]), ld4(bf(m.geom_quat, m.geom_quat_nb, w, 4 * m.ngeom) + 4 * id));
-  if (objtype == OBJ_SITE) return mul_quat(ld4(xquat + 4 * m.site_bodyid[id]), ld4(bf(m.site_quat, m.site_quat_nb, w, 4 * m.nsite) + 4 * id));
+  if (objtype == OBJ_GEOM) return mul_quat(ld4(xquat + 4 * m.geom_bodyid[id]), ld4(BF(m, geom_quat, w) + 4 * id));
+  if (objtype == OBJ_SITE) return mul_quat(ld4(xquat + 4 * m.site_bodyid[id]), ld4(BF(m, site_quat, w) + 4 * id));
   return Q4{1, 0, 0, 0};
 }
 // sensor.py:1066-1105 _cvel_offset and the velocity of the frame's origin
@@ -65,7 +65,7 @@ DEV void sens_vel(const MjhModel& m, const MjhData& d, int w, const SensFrame& f
 // accelerates at -gravity, every dof on the way down adds cdof_dot qvel + cdof qacc; one thread walks the body's dof chain
 DEV void sens_cacc(const MjhModel& m, const MjhData& d, int w, int body, V3& ang, V3& lin) {
   ang = V3{0, 0, 0};
-  lin = (m.disableflags & DSBL_GRAVITY) ? V3{0, 0, 0} : V3{0, 0, 0} - ld3(bf(m.opt_gravity, m.opt_gravity_nb, w, 3));
+  lin = (m.disableflags & DSBL_GRAVITY) ? V3{0, 0, 0} : V3{0, 0, 0} - ld3(BF(m, opt_gravity, w));
   int dof = m.body_lastdof[body];  // last dof of the body or of its nearest moving ancestor, -1 for static bodies
   const float* cdof = d.cdof + (size_t)w * m.nv * 6;
   const float* cdd = d.cdof_dot + (size_t)w * m.nv * 6;
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(256) k_sensor(MjhModel m, MjhData d, int stage
   else if (t == SENS_ACTUATORPOS) v[0] = d.actuator_length[(size_t)w * m.nu + id];
   else if (t == SENS_ACTUATORVEL) v[0] = d.actuator_velocity[(size_t)w * m.nu + id];
   else if (t == SENS_ACTUATORFRC) v[0] = d.actuator_force[(size_t)w * m.nu + id];
-  else if (t == SENS_MAGNETOMETER) put3(matT_mul(sens_frame(m, d, w, OBJ_SITE, id).mat, ld3(bf(m.opt_magnetic, m.opt_magnetic_nb, w, 3))));  // sensor.py:117-128
+  else if (t == SENS_MAGNETOMETER) put3(matT_mul(sens_frame(m, d, w, OBJ_SITE, id).mat, ld3(BF(m, opt_magnetic, w))));  // sensor.py:117-128
   else if (t == SENS_JOINTACTFRC) v[0] = d.qfrc_actuator[(size_t)w * m.nv + m.jnt_dofadr[id]];
   else if (t == SENS_E_POTENTIAL) v[0] = d.energy[2 * w];  // (k_energy ran just before)
   else if (t == SENS_E_KINETIC) v[0] = d.energy[2 * w + 1];

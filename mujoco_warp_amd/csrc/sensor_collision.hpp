@@ -53,7 +53,7 @@ DEV CcdGeom sc_geom(const MjhModel& m, const MjhData& d, int w, int g, int index
     nvert = m.mesh_vertnum[meshid];
     if (m.mesh_graphadr[meshid] >= 0) graph = m.mesh_graph + m.mesh_graphadr[meshid];
   }
-  return CcdGeom{type, ld3(d.geom_xpos + ((size_t)w * m.ngeom + g) * 3), d.geom_xmat + ((size_t)w * m.ngeom + g) * 9, ld3(bf(m.geom_size, m.geom_size_nb, w, 3 * m.ngeom) + 3 * g),
+  return CcdGeom{type, ld3(d.geom_xpos + ((size_t)w * m.ngeom + g) * 3), d.geom_xmat + ((size_t)w * m.ngeom + g) * 9, ld3(BF(m, geom_size, w) + 3 * g),
                  0.0f, vert, nvert, index, meshid, graph, index, nullptr};
 }
 DEV V3 sc_bcast(V3 a, int src) { return V3{__shfl(a.x, src, 64), __shfl(a.y, src, 64), __shfl(a.z, src, 64)}; }
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MJH_SC
   float* poly = smem + (size_t)wib * sc_lds_words(iters);
 
   const int type = m.sensor_type[i], objtype = m.sensor_objtype[i], objid = m.sensor_objid[i], reftype = m.sensor_reftype[i], refid = m.sensor_refid[i];
-  const float cutoff = m.sensor_cutoff[i], tol = bf(m.opt_ccd_tolerance, m.opt_ccd_tolerance_nb, w, 1)[0];
+  const float cutoff = m.sensor_cutoff[i], tol = BF(m, opt_ccd_tolerance, w)[0];
   const int n1 = objtype == SC_OBJ_BODY ? m.body_geomnum[objid] : 1, id1 = objtype == SC_OBJ_BODY ? m.body_geomadr[objid] : objid;
   const int n2 = reftype == SC_OBJ_BODY ? m.body_geomnum[refid] : 1, id2 = reftype == SC_OBJ_BODY ? m.body_geomadr[refid] : refid;
   const int npair = n1 * n2, gjk_it = min(m.ccd_iterations, CCD_MAX_ITER), epa_it = min(m.epa_iterations, CCD_MAX_ITER);

@@ -65,17 +65,17 @@ DEV void set_const_body(const MjhModel& m, float* smem, float* out_subtreemass, 
         *xanchor = S + lay.xanchor, *xaxis = S + lay.xaxis, *scom = S + lay.scom, *cinert = S + lay.cinert, *cdof = S + lay.cdof,
         *crb = S + lay.crb, *M = S + lay.M, *L = S + lay.L, *dinv = S + lay.dinv;
   // the world's rows of the batched inputs (coalesced), with the M-structure above: one batch of loads
-  gcopy<G>(mass, bf(m.body_mass, m.body_mass_nb, w, nbody), nbody, lig);
+  gcopy<G>(mass, BF(m, body_mass, w), nbody, lig);
   if (pos0) {
-    gcopy<G>(qpos, bf(m.qpos0, m.qpos0_nb, w, nq), nq, lig);
-    gcopy<G>(inertia, bf(m.body_inertia, m.body_inertia_nb, w, 3 * nbody), 3 * nbody, lig);
-    gcopy<G>(ipos, bf(m.body_ipos, m.body_ipos_nb, w, 3 * nbody), 3 * nbody, lig);
-    gcopy<G>(iquat, bf(m.body_iquat, m.body_iquat_nb, w, 4 * nbody), 4 * nbody, lig);
-    gcopy<G>(bpos, bf(m.body_pos, m.body_pos_nb, w, 3 * nbody), 3 * nbody, lig);
-    gcopy<G>(bquat, bf(m.body_quat, m.body_quat_nb, w, 4 * nbody), 4 * nbody, lig);
-    gcopy<G>(jpos, bf(m.jnt_pos, m.jnt_pos_nb, w, 3 * njnt), 3 * njnt, lig);
-    gcopy<G>(jaxis, bf(m.jnt_axis, m.jnt_axis_nb, w, 3 * njnt), 3 * njnt, lig);
-    gcopy<G>(armature, bf(m.dof_armature, m.dof_armature_nb, w, nv), nv, lig);
+    gcopy<G>(qpos, BF(m, qpos0, w), nq, lig);
+    gcopy<G>(inertia, BF(m, body_inertia, w), 3 * nbody, lig);
+    gcopy<G>(ipos, BF(m, body_ipos, w), 3 * nbody, lig);
+    gcopy<G>(iquat, BF(m, body_iquat, w), 4 * nbody, lig);
+    gcopy<G>(bpos, BF(m, body_pos, w), 3 * nbody, lig);
+    gcopy<G>(bquat, BF(m, body_quat, w), 4 * nbody, lig);
+    gcopy<G>(jpos, BF(m, jnt_pos, w), 3 * njnt, lig);
+    gcopy<G>(jaxis, BF(m, jnt_axis, w), 3 * njnt, lig);
+    gcopy<G>(armature, BF(m, dof_armature, w), nv, lig);
   }
   gsync();
 

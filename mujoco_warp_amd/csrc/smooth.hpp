@@ -276,17 +276,17 @@ DEV void mul_m_ld(const MStruct& ms, const float* M, const float* vec, float* re
 template <int G>
 DEV void actuator_vel_diag(const MjhModel& m, const MjhData& d, int w, int lig, float h, float* diag) {
   const int nu = m.nu, nv = m.nv;
-  const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
+  const float* gear = BF(m, actuator_gear, w);
   auto act_dv = [&](int u, float& val) __attribute__((always_inline)) {
-    const float bias_vel = m.actuator_biastype[u] == 1 ? bf(m.actuator_biasprm, m.actuator_biasprm_nb, w, 10 * nu)[10 * u + 2] : 0.0f;
-    const float gain_vel = m.actuator_gaintype[u] == 1 ? bf(m.actuator_gainprm, m.actuator_gainprm_nb, w, 10 * nu)[10 * u + 2] : 0.0f;
+    const float bias_vel = m.actuator_biastype[u] == 1 ? BF(m, actuator_biasprm, w)[10 * u + 2] : 0.0f;
+    const float gain_vel = m.actuator_gaintype[u] == 1 ? BF(m, actuator_gainprm, w)[10 * u + 2] : 0.0f;
     // the RAW control, not the clamped one, multiplies the velocity gain (derivative.py:159-161, mjd_actuator_vel)
     float ctrl = d.ctrl[(size_t)w * nu + u];
     if (m.actuator_dyntype[u] != 0) ctrl = d.act[(size_t)w * m.na + m.actuator_actadr[u]];
     const float dv = bias_vel + gain_vel * ctrl;
     if (dv == 0.0f) return false;
     if (m.actuator_forcelimited[u]) {
-      const float* fr = bf(m.actuator_forcerange, m.actuator_forcerange_nb, w, 2 * nu) + 2 * u;
+      const float* fr = BF(m, actuator_forcerange, w) + 2 * u;
       const float f = d.actuator_force[(size_t)w * nu + u];
       if (f <= fr[0] || f >= fr[1]) return false;
     }
@@ -660,11 +660,11 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
   } else if (first <= POS_KINEMATICS && valid) {
     gcopy<G>(qpos, d.qpos + (size_t)w * nq, nq, lig);
     gsync();
-    const float* qpos0 = bf(m.qpos0, m.qpos0_nb, w, nq);
-    const float* body_pos = bf(m.body_pos, m.body_pos_nb, w, 3 * nbody);
-    const float* body_quat = bf(m.body_quat, m.body_quat_nb, w, 4 * nbody);
-    const float* jnt_pos = bf(m.jnt_pos, m.jnt_pos_nb, w, 3 * njnt);
-    const float* jnt_axis = bf(m.jnt_axis, m.jnt_axis_nb, w, 3 * njnt);
+    const float* qpos0 = BF(m, qpos0, w);
+    const float* body_pos = BF(m, body_pos, w);
+    const float* body_quat = BF(m, body_quat, w);
+    const float* jnt_pos = BF(m, jnt_pos, w);
+    const float* jnt_axis = BF(m, jnt_axis, w);
     kin_levels<G>(m, true, d.mocap_pos + (size_t)w * m.nmocap * 3, d.mocap_quat + (size_t)w * m.nmocap * 4, qpos, qpos0, body_pos, body_quat, jnt_pos, jnt_axis, xpos, xquat,
                   xanchor, xaxis, lig);
   }
@@ -672,16 +672,16 @@ DEV void fwd_pos_impl(const MjhModel& m, const MjhData& d, int first, int last, 
   if (!valid) return;
   pc.mark(5);
   // model constants: from the LDS table (TAB) or from the model arrays (batched fields)
-  const float* body_ipos = TAB ? pt.ipos : bf(m.body_ipos, m.body_ipos_nb, w, 3 * nbody);
-  const float* body_iquat = TAB ? pt.iquat : bf(m.body_iquat, m.body_iquat_nb, w, 4 * nbody);
-  const float* geom_pos = TAB ? pt.gpos : bf(m.geom_pos, m.geom_pos_nb, w, 3 * m.ngeom);
-  const float* geom_quat = TAB ? pt.gquat : bf(m.geom_quat, m.geom_quat_nb, w, 4 * m.ngeom);
-  const float* site_pos = TAB ? pt.spos : bf(m.site_pos, m.site_pos_nb, w, 3 * m.nsite);
-  const float* site_quat = TAB ? pt.squat : bf(m.site_quat, m.site_quat_nb, w, 4 * m.nsite);
-  const float* body_mass = TAB ? pt.mass : bf(m.body_mass, m.body_mass_nb, w, nbody);
-  const float* body_subtreemass = TAB ? pt.submass : bf(m.body_subtreemass, m.body_subtreemass_nb, w, nbody);
-  const float* body_inertia = TAB ? pt.inertia : bf(m.body_inertia, m.body_inertia_nb, w, 3 * nbody);
-  const float* armature = TAB ? pt.armature : bf(m.dof_armature, m.dof_armature_nb, w, nv);
+  const float* body_ipos = TAB ? pt.ipos : BF(m, body_ipos, w);
+  const float* body_iquat = TAB ? pt.iquat : BF(m, body_iquat, w);
+  const float* geom_pos = TAB ? pt.gpos : BF(m, geom_pos, w);
+  const float* geom_quat = TAB ? pt.gquat : BF(m, geom_quat, w);
+  const float* site_pos = TAB ? pt.spos : BF(m, site_pos, w);
+  const float* site_quat = TAB ? pt.squat : BF(m, site_quat, w);
+  const float* body_mass = TAB ? pt.mass : BF(m, body_mass, w);
+  const float* body_subtreemass = TAB ? pt.submass : BF(m, body_subtreemass, w);
+  const float* body_inertia = TAB ? pt.inertia : BF(m, body_inertia, w);
+  const float* armature = TAB ? pt.armature : BF(m, dof_armature, w);
   const int* geom_bodyid = TAB ? pt.gbody : m.geom_bodyid;
   const int* site_bodyid = TAB ? pt.sbody : m.site_bodyid;
   const int* body_subtreenum = TAB ? pt.subnum : m.body_subtreenum;
@@ -890,7 +890,7 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
     if constexpr (TRN) {
       for (int u = lig; u < nu; u += G) d.actuator_velocity[(size_t)w * nu + u] = trn_row_dot(m, d, w, u, qvel);
     } else {
-      const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
+      const float* gear = BF(m, actuator_gear, w);
       for (int u = lig; u < nu; u += G)
         d.actuator_velocity[(size_t)w * nu + u] = gear[6 * u] * qvel[m.jnt_dofadr[m.actuator_trnid[2 * u]]];
     }
@@ -903,9 +903,9 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
 
   // ---- passive (passive.py:74-210 spring/damper, 275-306 gravcomp, 631-668 sum) --------------------------
   if (first <= VEL_PASSIVE) {
-    const float* stiff = bf(m.jnt_stiffness, m.jnt_stiffness_nb, w, njnt);
-    const float* damp = bf(m.dof_damping, m.dof_damping_nb, w, nv);
-    const float* qspring = bf(m.qpos_spring, m.qpos_spring_nb, w, nq);
+    const float* stiff = BF(m, jnt_stiffness, w);
+    const float* damp = BF(m, dof_damping, w);
+    const float* qspring = BF(m, qpos_spring, w);
     for (int i = lig; i < nv; i += G) {
       fspring[i] = 0.0f;
       fgrav[i] = 0.0f;
@@ -930,9 +930,9 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
       }
     }
     if (!(dsbl & DSBL_GRAVITY)) {
-      const float* gcomp = bf(m.body_gravcomp, m.body_gravcomp_nb, w, nbody);
-      const float* mass = bf(m.body_mass, m.body_mass_nb, w, nbody);
-      const float* grav = bf(m.opt_gravity, m.opt_gravity_nb, w, 3);
+      const float* gcomp = BF(m, body_gravcomp, w);
+      const float* mass = BF(m, body_mass, w);
+      const float* grav = BF(m, opt_gravity, w);
       const int nw = (nv + 31) / 32;
       for (int b = 1; b < nbody; ++b) {
         const float gc = gcomp[b];
@@ -962,7 +962,7 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
       gcopy<G>(cdof_dot, d.cdof_dot + (size_t)w * 6 * nv, 6 * nv, lig);
       gsync();
     }
-    const float* grav = bf(m.opt_gravity, m.opt_gravity_nb, w, 3);
+    const float* grav = BF(m, opt_gravity, w);
     for (int b = lig; b < nbody; b += G) {
       float ca[6] = {0, 0, 0, 0, 0, 0};
       if (!(dsbl & DSBL_GRAVITY)) {
@@ -1017,13 +1017,13 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
 
   // ---- fwd_actuation (forward.py:756-1149; NONE/INTEGRATOR/FILTER dyn, FIXED/AFFINE gain, NONE/AFFINE bias) --
   if (first <= VEL_ACTUATION) {
-    const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * nu);
+    const float* gear = BF(m, actuator_gear, w);
     for (int u = lig; u < nu; u += G) {
       float force = 0.0f;
       if (!(dsbl & DSBL_ACTUATION)) {
         float ctrl = d.ctrl[(size_t)w * nu + u];
         if (m.actuator_ctrllimited[u] && !(dsbl & DSBL_CLAMPCTRL)) {
-          const float* cr = bf(m.actuator_ctrlrange, m.actuator_ctrlrange_nb, w, 2 * nu) + 2 * u;
+          const float* cr = BF(m, actuator_ctrlrange, w) + 2 * u;
           ctrl = clampf(ctrl, cr[0], cr[1]);
         }
         float ctrl_act = ctrl;
@@ -1033,7 +1033,7 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
           const float act = d.act[(size_t)w * m.na + adr];
           float act_dot = 0.0f;
           if (dyn == 1) act_dot = ctrl;
-          else if (dyn == 2 || dyn == 3) act_dot = (ctrl - act) / fmaxf(MJ_MINVAL, bf(m.actuator_dynprm, m.actuator_dynprm_nb, w, 10 * nu)[10 * u]);
+          else if (dyn == 2 || dyn == 3) act_dot = (ctrl - act) / fmaxf(MJ_MINVAL, BF(m, actuator_dynprm, w)[10 * u]);
           d.act_dot[(size_t)w * m.na + adr] = act_dot;
           ctrl_act = act;
         }
@@ -1046,13 +1046,13 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
           length = qpos[m.jnt_qposadr[jid]] * gear[6 * u];
           velocity = gear[6 * u] * qvel[m.jnt_dofadr[jid]];
         }
-        const float* gp = bf(m.actuator_gainprm, m.actuator_gainprm_nb, w, 10 * nu) + 10 * u;
-        const float* bp = bf(m.actuator_biasprm, m.actuator_biasprm_nb, w, 10 * nu) + 10 * u;
+        const float* gp = BF(m, actuator_gainprm, w) + 10 * u;
+        const float* bp = BF(m, actuator_biasprm, w) + 10 * u;
         const float gain = m.actuator_gaintype[u] == 0 ? gp[0] : gp[0] + gp[1] * length + gp[2] * velocity;
         const float bias = m.actuator_biastype[u] == 0 ? 0.0f : bp[0] + bp[1] * length + bp[2] * velocity;
         force = gain * ctrl_act + bias;
         if (m.actuator_forcelimited[u]) {
-          const float* fr = bf(m.actuator_forcerange, m.actuator_forcerange_nb, w, 2 * nu) + 2 * u;
+          const float* fr = BF(m, actuator_forcerange, w) + 2 * u;
           force = clampf(force, fr[0], fr[1]);
         }
         if constexpr (!TRN) d.actuator_length[(size_t)w * nu + u] = length;
@@ -1089,7 +1089,7 @@ DEV void fwd_vel_body(const MjhModel& m, const MjhData& d, int first, int last, 
     gsync();
     if (nu > 0 && !(dsbl & DSBL_ACTUATION)) {  // forward.py:1121-1150 _qfrc_actuator_gravcomp_limits: actuator-level gravity compensation, then the
       // joint's actuatorfrcrange -- not without actuators / with actuation disabled: the reference returns with qfrc_actuator = 0 (forward.py:1155-1159)
-      const float* afr = bf(m.jnt_actfrcrange, m.jnt_actfrcrange_nb, w, 2 * njnt);
+      const float* afr = BF(m, jnt_actfrcrange, w);
       for (int i = lig; i < nv; i += G) {
         const int j = m.dof_jntid[i];
         float q = factuator[i];

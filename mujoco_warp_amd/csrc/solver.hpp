@@ -309,7 +309,7 @@ template <int NV4, int G>
 DEV float impfast_acc(const MjhModel& m, const MjhData& d, int w, int lig, bool active, const float (&mrow)[4 * NV4], float Ma, float* scratch) {
   constexpr int NVR = 4 * NV4;
   float *diag = scratch, *panel = scratch + G, *vec = panel + 4 * G, *save = vec + G;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   diag[lig] = 0.0f;
   gsync();
   if (!(m.disableflags & DSBL_ACTUATION)) actuator_vel_diag<G>(m, d, w, lig, h, diag);
@@ -317,7 +317,7 @@ DEV float impfast_acc(const MjhModel& m, const MjhData& d, int w, int lig, bool 
   float dg = 0.0f;
   if (active) {
     dg = diag[lig];
-    if (!(m.disableflags & DSBL_DAMPER)) dg += h * bf(m.dof_damping, m.dof_damping_nb, w, m.nv)[lig];
+    if (!(m.disableflags & DSBL_DAMPER)) dg += h * BF(m, dof_damping, w)[lig];
   }
   float hh[NVR];
 #pragma unroll
@@ -378,7 +378,7 @@ DEV void row_force(int kind, float ja, float D, bool has_fl, const float* floss,
 template <int G>
 DEV void euler_advance(const MjhModel& m, const MjhData& d, int w, int lig, bool active, float qacc_i, float* vbuf, float warm_i) {
   const int nv = m.nv;
-  const float h = bf(m.opt_timestep, m.opt_timestep_nb, w, 1)[0];
+  const float h = BF(m, opt_timestep, w)[0];
   const size_t vo = (size_t)w * nv;
   if (active) {
     const float v = d.qvel[vo + lig] + qacc_i * h;
@@ -1018,7 +1018,7 @@ DEV void solve_body(const MjhModel& m, const MjhData& d, float* smem, const Blk&
         const int* cri = reinterpret_cast<const int*>(cr);
         if (cri[24] > 1) {
           const int r0 = r - dimid, dim = min(cri[29], nefc - r0);
-          const float impr2 = bf(m.opt_impratio_invsqrt, m.opt_impratio_invsqrt_nb, w, 1)[0];
+          const float impr2 = BF(m, opt_impratio_invsqrt, w)[0];
           const float mu = cr[14] * impr2;
           rkind[k] = dimid == 0 ? 4 : 5;
           rmu[k] = mu;
@@ -1049,9 +1049,9 @@ DEV void solve_body(const MjhModel& m, const MjhData& d, float* smem, const Blk&
   gsync();
 
   pc.mark(2);
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float ls_tolerance = bf(m.opt_ls_tolerance, m.opt_ls_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float ls_tolerance = BF(m, opt_ls_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
   const float scale = meaninertia * (float)nv_all;
   const float rscale = 1.0f / scale;
 

@@ -126,7 +126,7 @@ DEV void solve_big_body(const MjhModel& m, const MjhData& d, float* smem, const 
         const int* cri = reinterpret_cast<const int*>(cr);
         if (cri[24] > 1) {
           const int r0 = r - dimid, dim = min(cri[29], nefc - r0);
-          const float mu = cr[14] * bf(m.opt_impratio_invsqrt, m.opt_impratio_invsqrt_nb, w, 1)[0];
+          const float mu = cr[14] * BF(m, opt_impratio_invsqrt, w)[0];
           kind[r] = dimid == 0 ? 4 : 5;
           rmu[r] = mu;
           rs[r] = dimid == 0 ? mu : cr[CON_FRICTION_WORD(dimid - 1)];
@@ -182,9 +182,9 @@ DEV void solve_big_body(const MjhModel& m, const MjhData& d, float* smem, const 
     }
   };
 
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float ls_tolerance = bf(m.opt_ls_tolerance, m.opt_ls_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float ls_tolerance = BF(m, opt_ls_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
   const float scale = meaninertia * (float)nv, rscale = 1.0f / scale;
   const int maxiter = m.iterations, ls_iterations = m.ls_iterations;
   const bool has_fl = nf > 0;

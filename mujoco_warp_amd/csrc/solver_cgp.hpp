@@ -432,9 +432,9 @@ DEV void solve_cgp_body(const MjhModel& m, const MjhData& d, float* smem, int sl
     for (int k = 0; k < NR; ++k) rja[k] = rkind[k] != 3 ? jq[k] - rja[k] : 0.0f;
   }
   pc.mark(2);
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float ls_tolerance = bf(m.opt_ls_tolerance, m.opt_ls_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float ls_tolerance = BF(m, opt_ls_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
   const float scale = meaninertia * (float)nv;
   const float rscale = 1.0f / scale;
   // J^T f: lane (cq, rg) reads the columns 4 cq .. 4 cq + 3 of the rows rg + 4 i: one base address, every row an immediate offset

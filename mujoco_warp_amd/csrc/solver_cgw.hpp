@@ -210,9 +210,9 @@ DEV void solve_cgw_body(const MjhModel& m, const MjhData& d, float* smem, const 
   const bool inrow = lig < njmax;
   const float rD_raw = inrow ? d.efc_D[eo + lig] : 0.0f;
   const float aref = inrow ? d.efc_aref[eo + lig] : 0.0f;
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float ls_tolerance = bf(m.opt_ls_tolerance, m.opt_ls_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float ls_tolerance = BF(m, opt_ls_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
 
   const int nefc_all = min(nefc_raw, njmax);
   if (nefc_all <= nefc_lo || nefc_all > nefc_hi) return;  // (two-size dispatch: see solve_body)

@@ -296,9 +296,9 @@ DEV void newton_pair(const MjhModel& m, const MjhData& d, float* S, const Newton
   gsync();
   pc.mark(2);
 
-  const float tolerance = bf(m.opt_tolerance, m.opt_tolerance_nb, w, 1)[0];
-  const float ls_tolerance = bf(m.opt_ls_tolerance, m.opt_ls_tolerance_nb, w, 1)[0];
-  const float meaninertia = bf(m.stat_meaninertia, m.stat_meaninertia_nb, w, 1)[0];
+  const float tolerance = BF(m, opt_tolerance, w)[0];
+  const float ls_tolerance = BF(m, opt_ls_tolerance, w)[0];
+  const float meaninertia = BF(m, stat_meaninertia, w)[0];
   const float scale = meaninertia * (float)nv;
   const float rscale = 1.0f / scale;
   const int maxiter = m.iterations, ls_iterations = m.ls_iterations;

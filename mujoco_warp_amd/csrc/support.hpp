@@ -79,14 +79,14 @@ __global__ void __launch_bounds__(256) k_energy(MjhModel m, MjhData d) {
   const int lig = threadIdx.x & (G - 1);
   const int w = blockIdx.x * (blockDim.x / G) + threadIdx.x / G;
   if (w >= d.nworld) return;
-  const V3 g = ld3(bf(m.opt_gravity, m.opt_gravity_nb, w, 3));
-  const float* mass = bf(m.body_mass, m.body_mass_nb, w, m.nbody);
+  const V3 g = ld3(BF(m, opt_gravity, w));
+  const float* mass = BF(m, body_mass, w);
   float pot = 0.0f;
   if (!(m.disableflags & DSBL_GRAVITY))
     for (int b = 1 + lig; b < m.nbody; b += G) pot -= mass[b] * dot(g, ld3(d.xipos + ((size_t)w * m.nbody + b) * 3));
   if (!(m.disableflags & DSBL_SPRING)) {
-    const float* stiff = bf(m.jnt_stiffness, m.jnt_stiffness_nb, w, m.njnt);
-    const float* qs = bf(m.qpos_spring, m.qpos_spring_nb, w, m.nq);
+    const float* stiff = BF(m, jnt_stiffness, w);
+    const float* qs = BF(m, qpos_spring, w);
     const float* qpos = d.qpos + (size_t)w * m.nq;
     for (int j = lig; j < m.njnt; j += G) {
       const float kk = stiff[j];
@@ -146,9 +146,9 @@ __global__ void __launch_bounds__(256) k_subtree_vel(MjhModel m, MjhData d) {
   float* lin = smem + (size_t)gib * 9 * nb;  // m v per body, then T
   float* lv = lin + 3 * nb;                  // subtree linear velocity
   float* acc = lv + 3 * nb;                  // A + T per body
-  const float* mass = bf(m.body_mass, m.body_mass_nb, w, nb);
-  const float* inertia = bf(m.body_inertia, m.body_inertia_nb, w, 3 * nb);
-  const float* stm = bf(m.body_subtreemass, m.body_subtreemass_nb, w, nb);
+  const float* mass = BF(m, body_mass, w);
+  const float* inertia = BF(m, body_inertia, w);
+  const float* stm = BF(m, body_subtreemass, w);
   float* linvel = d.subtree_linvel + (size_t)w * nb * 3;
   float* angmom = d.subtree_angmom + (size_t)w * nb * 3;
   const float* scom = d.subtree_com + (size_t)w * nb * 3;
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(256) k_rne_postconstraint(MjhModel m, MjhData 
           const int o1 = m.eq_obj1id[e], o2 = m.eq_obj2id[e];
           const int b1 = site ? m.site_bodyid[o1] : o1, b2 = site ? m.site_bodyid[o2] : o2;
           if ((b1 == b || b2 == b) && r + 2 < d.njmax) {
-            const float* data = bf(m.eq_data, m.eq_data_nb, w, 11 * m.neq) + 11 * e;
+            const float* data = BF(m, eq_data, w) + 11 * e;
             const V3 force = ld3(efc_force + r);
             for (int side = 0; side < 2; ++side) {
               if ((side ? b2 : b1) != b) continue;
@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(256) k_rne_postconstraint(MjhModel m, MjhData 
     for (int k = 0; k < 6; ++k) loc[6 * b + k] = a[k];
   }
   gsync();
-  const V3 g = ld3(bf(m.opt_gravity, m.opt_gravity_nb, w, 3));
+  const V3 g = ld3(BF(m, opt_gravity, w));
   const bool grav = !(m.disableflags & DSBL_GRAVITY);
   for (int b = lig; b < nb; b += G) {
     float a[6] = {0, 0, 0, grav ? -g.x : 0.0f, grav ? -g.y : 0.0f, grav ? -g.z : 0.0f};

@@ -25,7 +25,7 @@ DEV V3 trn_gear_axis(V3 axis, const float* quat, bool inparent) {
 }
 
 DEV float trn_length(const MjhModel& m, const MjhData& d, int w, int u) {
-  const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * m.nu) + 6 * u;
+  const float* gear = BF(m, actuator_gear, w) + 6 * u;
   const int type = m.actuator_trntype[u], id0 = m.actuator_trnobj[2 * u], id1 = m.actuator_trnobj[2 * u + 1];
   if (type == TRN_JOINT || type == TRN_JOINTINPARENT) {
     const float* q = d.qpos + (size_t)w * m.nq + m.jnt_qposadr[id0];
@@ -42,7 +42,7 @@ DEV float trn_length(const MjhModel& m, const MjhData& d, int w, int u) {
   if (gt.x != 0.0f || gt.y != 0.0f || gt.z != 0.0f) length += dot(matT_mul(rmat, ld3(sx + 3 * id0) - ld3(sx + 3 * id1)), gt);
   if (gr.x != 0.0f || gr.y != 0.0f || gr.z != 0.0f) {
     // the two site quaternions from their bodies' (site_quat o xquat, the reference's order: smooth.py:2642)
-    const float* sq = bf(m.site_quat, m.site_quat_nb, w, 4 * m.nsite);
+    const float* sq = BF(m, site_quat, w);
     const float* xq = d.xquat + (size_t)w * m.nbody * 4;
     const Q4 quat = mul_quat(ld4(sq + 4 * id0), ld4(xq + 4 * m.site_bodyid[id0]));
     const Q4 refquat = mul_quat(ld4(sq + 4 * id1), ld4(xq + 4 * m.site_bodyid[id1]));
@@ -53,7 +53,7 @@ DEV float trn_length(const MjhModel& m, const MjhData& d, int w, int u) {
 
 DEV float trn_moment(const MjhModel& m, const MjhData& d, int w, int k) {
   const int u = m.moment_rowid[k], i = m.moment_colind[k];
-  const float* gear = bf(m.actuator_gear, m.actuator_gear_nb, w, 6 * m.nu) + 6 * u;
+  const float* gear = BF(m, actuator_gear, w) + 6 * u;
   const int type = m.actuator_trntype[u], id0 = m.actuator_trnobj[2 * u], id1 = m.actuator_trnobj[2 * u + 1];
   if (type == TRN_JOINT || type == TRN_JOINTINPARENT) {
     const int jt = m.jnt_type[id0], c = i - m.jnt_dofadr[id0];

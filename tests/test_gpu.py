@@ -1004,6 +1004,42 @@ def test_batched_gravity_and_mass():
   assert z[3] == z[1]
 
 
+@pytest.mark.parametrize("scene", ["humanoid_newton", "humanoid_cg", "connect"])
+def test_every_batched_field_read_from_its_second_row(scene):
+  """Every batchable Model field carries 2 rows of identical content and 3 worlds run: worlds 0 and 2 read row 0, world 1 reads row 1 -- through
+  reset_data, set_const and 3 steps.  A read with a wrong row size or a wrong batch count lands outside row 1 in world 1 only, so the three
+  worlds must agree to the last bit.  (The connect scene reads the eq_* rows, body_invweight0 and, in the reset, the mocap bodies' rows.)"""
+  from mujoco_warp_amd import io as mjio
+
+  if scene == "connect":
+    from test_connect import MIXED_XML
+
+    mjm = mjw.mjcf.from_xml_string(MIXED_XML)
+    nconmax, njmax = 8, 32
+  else:
+    mjm = mjw.mjcf.load_xml(conftest.HUMANOID_XML)
+    mjm.opt.solver = int(mjw.SolverType.NEWTON if scene == "humanoid_newton" else mjw.SolverType.CG)
+    nconmax, njmax = 24, 64
+  m = mjw.put_model(mjm, batch_sizes={name: 2 for name in mjio._BATCHED_MODEL_FIELDS})
+  cm = mjio.c_model(m)
+  assert len(mjio._BATCHED_MODEL_FIELDS) == 56 and all(getattr(cm, name + "_nb") == 2 for name in mjio._BATCHED_MODEL_FIELDS)
+  d = mjw.make_data(mjm, nworld=3, nconmax=nconmax, njmax=njmax)
+  mjw.reset_data(m, d)
+  mjw.set_const(m, d)
+  if scene != "connect":
+    d.qpos.assign(np.tile(np.asarray(mjm.key_qpos[0], dtype=np.float32), (3, 1)))  # the squat: feet on the floor
+  d.ctrl.assign(np.tile(0.3 * np.cos(np.arange(mjm.nu, dtype=np.float32)), (3, 1)))
+  for _ in range(3):
+    mjw.step(m, d)
+  torch.cuda.synchronize()
+  assert (d.overflow.numpy() == 0).all()
+  assert int(d.nefc.numpy()[0]) > 0 and (scene == "connect" or int(d.ws_ncon.numpy()[0]) > 0)
+  for name in ("qpos", "qvel", "qacc", "qacc_warmstart", "sensordata", "ws_ncon", "nefc", "ne", "nf", "nl"):
+    a = getattr(d, name).numpy()
+    assert np.isfinite(a).all(), name
+    assert (a[1] == a[0]).all() and (a[2] == a[0]).all(), (name, a)
+
+
 @pytest.mark.parametrize("override", [[], ["opt.solver=cg"], ["opt.solver=pgs"], ["opt.integrator=RK4"], ["opt.integrator=implicitfast"]])
 def test_graph_replay_matches_eager(override):
   """hipGraph capture of one step (side-stream fork/join for Newton, fused Euler for CG, four forwards for RK4) replays bit for bit."""

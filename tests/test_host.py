@@ -604,6 +604,29 @@ def test_launch_decisions_travel_in_the_plan_not_in_globals():
   assert ladders <= 2, ladders
 
 
+def test_batched_model_fields_are_read_through_the_accessor():
+  """A kernel reads a batched Model field (one with a companion <field>_nb) only as BF(m, field, w) (dev_common.hpp), which takes the
+  companion and the row size from the field's name.  bf() is called by BF alone, nothing hand-rolls `w % m.<field>_nb`, and a direct
+  mention of m.<field> is either a host null check or sits in a file that also holds the guard <field>_nb <= 1 for that field (the
+  staged-table fills, which read row 0)."""
+  batched = [n[:-3] for n, kind, ptr in _abi.MODEL_FIELDS if n.endswith("_nb")]
+  assert len(batched) == 56
+  text = {f: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", t, flags=re.S)) for f, t in _csrc_text().items()}
+  calls = [(f, line.strip()) for f, t in text.items() for line in t.splitlines() if re.search(r"\bbf\(", line)]
+  assert len(calls) == 2 and all(f == "dev_common.hpp" for f, _ in calls), calls
+  assert calls[0][1].startswith("DEV const float* bf(const float* p, int nb, int w, int stride)") and calls[1][1].startswith("#define BF(m, field, w) bf(")
+  assert sum(len(re.findall(r"\bBF\(m, \w+, w\)", t)) for t in text.values()) >= 150  # (the scan sees the sites)
+  bad = []
+  for f, t in text.items():
+    bad += [(f, s) for s in re.findall(r"%\s*m(?:\.|->)\w+_nb\b", t)]
+    for mm in re.finditer(r"(!?)\bm(\.|->)(%s)\b" % "|".join(batched), t):
+      null_check = mm.group(1) == "!" and mm.group(2) == "->"
+      guarded = re.search(r"\b%s_nb <= 1\b" % mm.group(3), t)
+      if not null_check and not guarded:
+        bad.append((f, mm.group(0)))
+  assert not bad, bad
+
+
 def test_dev_knobs_refuses_to_shadow_an_environment_value(monkeypatch):
   """A knob that came from the environment snapshot cannot be read back (no getter in the ABI), so dev_knobs raises instead of losing it."""
   monkeypatch.setattr(_abi, "_env_knobs", {"MJH_CG_KERNEL"})

@@ -1,7 +1,10 @@
 """CPU tests of the IO boundary's single source of shapes and dtypes: types.array_fields drives put_model, make_data and put_data."""
 
+import os
+import re
 import sys
 
+import numpy as np
 import pytest
 
 import conftest
@@ -58,3 +61,26 @@ def test_missing_required_field_raises_and_optional_does_not(humanoid):
   m = mjw.put_model(make_host_tables.Hidden(humanoid, {"geom_rgba", "site_size", "sensor_type"}))
   assert m.geom_rgba.shape == (humanoid.ngeom, 4) and (m.geom_rgba.numpy() == [0.5, 0.5, 0.5, 1.0]).all()
   assert m.site_size.shape == (humanoid.nsite, 3) and m.nsensor == 0
+
+
+def test_row_size_table_matches_the_schema():
+  """csrc/dev_common.hpp's MJH_ROW_<field> table (the one statement of a batched field's row size on the C side) has exactly the header's
+  <field>_nb fields, and every entry is the product of the shape types.py declares behind '*'.  The sizes are pairwise coprime and prime, so no
+  mixed-up size name or factor can give the right product."""
+  text = open(os.path.join(os.path.dirname(_abi.__file__), "csrc", "dev_common.hpp")).read()
+  text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+  entries = re.findall(r"^#define MJH_ROW_(\w+)\(m\) (.+)$", text, flags=re.M)
+  table = dict(entries)
+  assert len(entries) == len(table), "a field is listed twice"
+  batched = {n[:-3] for n, kind, ptr in _abi.MODEL_FIELDS if n.endswith("_nb")}
+  assert len(batched) == 56 and set(table) == batched
+  sizes = {"nq": 7, "nv": 5, "nbody": 11, "njnt": 13, "ngeom": 17, "nsite": 19, "nu": 23, "neq": 29}
+  declared = {prefix + n: spec[0] for prefix, cls in (("opt_", types.Option), ("stat_", types.Statistic), ("", types.Model))
+              for n, spec in types.array_fields(cls).items()}  # (the ABI names, as io.c_model maps them)
+  for name, expr in table.items():
+    shape = declared[name]
+    assert shape[0] == "*", name
+    want = int(np.prod(types.eval_shape(shape[1:], sizes), dtype=np.int64))
+    expr = re.sub(r"\(m\)\.(\w+)", r"\1", expr)  # over m only: what is left must be integers and size names
+    assert re.fullmatch(r"[\w\s*()]+", expr), (name, expr)
+    assert int(eval(expr, {"__builtins__": {}}, sizes)) == want, (name, expr, shape)
