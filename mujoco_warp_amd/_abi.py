@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libmjhip.so")
 # headers they include
 UNITS = ["mjhip.hip", "solve_cgp.hip", "solve_cg32.hip", "solve_ell_newton32_r1.hip", "solve_cgw.hip", "solve_newton32.hip", "solve_cg64.hip", "solve_newton64.hip", "solve_ell_cg32.hip", "solve_ell_newton32.hip",
          "solve_ell_cg64.hip", "solve_ell_newton64.hip", "solve_tree_cg.hip", "solve_tree_newton.hip", "solve_tree_ell_cg.hip", "solve_tree_ell_newton.hip", "pgs_tu.hip", "solve_big.hip", "render_tu.hip", "set_const_tu.hip", "sensor_contact_tu.hip", "sensor_collision_tu.hip", "transmission_tu.hip", "history_tu.hip", "reset_tu.hip", "inverse_tu.hip", "build_id.hip"]
-HEADERS = ["host.hpp", "solve_tu.hpp", "solve_tree.hpp", "dev_common.hpp", "smooth.hpp", "collide.hpp", "constraint.hpp", "solver.hpp", "solver_cgp.hpp", "solver_cgw.hpp", "solver_newton.hpp", "solver_big.hpp", "pgs.hpp",
+HEADERS = ["host.hpp", "solve_tu.hpp", "solve_tree.hpp", "dev_common.hpp", "smooth.hpp", "collide.hpp", "constraint.hpp", "linesearch.hpp", "solver.hpp", "solver_cgp.hpp", "solver_cgw.hpp", "solver_newton.hpp", "solver_big.hpp", "pgs.hpp",
            "integrate.hpp", "implicit.hpp", "pgs_big.hpp", "sleep.hpp", "convex.hpp", "sensor.hpp", "support.hpp", "ray.hpp", "contact_rec.hpp", "render.hpp", "set_const.hpp", "sensor_contact.hpp", "site_inside.hpp", "sensor_collision.hpp", "transmission.hpp", "history.hpp", "reset.hpp", "inverse.hpp"]
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in UNITS + HEADERS]
 # -fno-slp-vectorize: the SLP vectoriser packs scalar float ops into v_pk_* pairs, which on gfx950 issue at HALF the rate of the

@@ -17,6 +17,7 @@
 // state out.
 #pragma once
 #include "dev_common.hpp"
+#include "linesearch.hpp"  // the line search (solver.py:835-1347): ray evaluators, ls_bracket, line_search_rows
 #include "smooth.hpp"
 
 // ---- DPP reduction over a 32-lane group; every lane receives the total ---------------------------------
@@ -109,87 +110,20 @@ DEV void gsum_sel(float (&v)[N]) {
 }
 // (A butterfly all-reduce -- quad_perm, row_half_mirror, row_mirror, v_permlane16_swap or ds_swizzle -- is two VALU ops
 // shorter and passes in isolation, but inside k_solve it broke parity with both cross-row variants; not pursued.)
-// division for step-size candidates and ratios that only steer the search (v_rcp_f32, 1 ulp; an IEEE divide is ~10 ops)
-DEV float fast_div(float x, float y) { return x * __builtin_amdgcn_rcpf(y != 0.0f ? y : MJ_MINVAL); }
 
-// ---- dense Cholesky with lane i owning row i (NVR <= 32), all indices compile-time ----------------------
-// h: row i of the SPD matrix on entry, row i of L on exit (entries above the diagonal are junk);
-// lt: column i of L below the diagonal (for the transposed solve); rdiag = 1 / L[i][i].
-// `col` is an LDS scratch of max(64, 8*JS) floats private to the group.  Lanes >= nv must hold identity rows.
-template <int NVR, int JS, int G>
-DEV void chol_factor_rows(float (&h)[NVR], float (&lt)[NVR], float& rdiag, float* col, int lig) {
-  const bool own = lig < NVR;
-  const int ligc = own ? lig : NVR - 1;
-  rdiag = 1.0f;
-#pragma unroll
-  for (int j = 0; j < NVR; ++j) {  // right-looking; pivot column broadcast through LDS (double buffered)
-    float* cb = col + (j & 1) * G;
-    // (unconditional: lanes past the matrix write slots nobody reads; a branch here lets LLVM sink the updates below across it)
-    cb[lig] = h[j];
-    gsync();
-    // pivot by v_readlane (off the LDS round trip); 1/sqrt = v_rsq_f32 + one Newton step (~0.5 ulp)
-    const float pv = fmaxf(bcastg<G>(h[j], j), MJ_MINVAL);
-    float inv = __builtin_amdgcn_rsqf(pv);
-    inv = inv * (1.5f - 0.5f * pv * inv * inv);
-    const float piv = pv * inv;
-    const float lij = (lig == j) ? piv : h[j] * inv;
-    h[j] = lij;
-    rdiag = (lig == j) ? inv : rdiag;
-    const float t = lij * inv;
-#pragma unroll
-    for (int k = j + 1; k < NVR; ++k) h[k] -= t * cb[k];
-  }
-  gsync();
-#pragma unroll
-  for (int c0 = 0; c0 < NVR; c0 += 8) {  // column i of L: rows pass through an 8-row LDS tile
-    if (lig >= c0 && lig < c0 + 8 && own) {
-#pragma unroll
-      for (int c4 = 0; c4 < NVR / 4; ++c4)
-        *reinterpret_cast<float4*>(col + (lig - c0) * JS + 4 * c4) = make_float4(h[4 * c4], h[4 * c4 + 1], h[4 * c4 + 2], h[4 * c4 + 3]);
-    }
-    gsync();
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      if (c0 + kk < NVR) {
-        const float v = col[kk * JS + ligc];
-        lt[c0 + kk] = (own && c0 + kk > lig) ? v : 0.0f;
-      }
-    }
-    gsync();
-  }
-}
-// x = (L L^T)^-1 g for the lane's component; broadcasts via v_readlane (no LDS traffic)
-template <int NVR, int G>
-DEV float chol_solve_rows(const float (&h)[NVR], const float (&lt)[NVR], float rdiag, float g) {
-  const int lig = threadIdx.x & (G - 1);
-  float acc = g, y = 0.0f, x = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NVR; ++k) {
-    const float yk = bcastg<G>(acc * rdiag, k);
-    if (lig == k) y = yk;
-    acc -= h[k] * yk;
-  }
-  acc = y;
-#pragma unroll
-  for (int k = NVR - 1; k >= 0; --k) {
-    const float xk = bcastg<G>(acc * rdiag, k);
-    if (lig == k) x = xk;
-    acc -= lt[k] * xk;
-  }
-  return x;
-}
-
-// ---- the same solve by a BLOCKED right-looking Cholesky (round 2 for the MFMA Newton kernel, round 3 generic in the group size):
-// factorisation, forward and backward substitution in one routine, nothing but the H row (NVR registers) held across it.
+// ---- x = H^-1 g by a BLOCKED right-looking Cholesky with lane i owning row i (NVR <= G), all indices compile-time: THE dense solve of
+// every kernel here (solve_body, the MFMA Newton kernel's newton_pair, the fused implicitfast update).  Factorisation, forward and
+// backward substitution in one routine, nothing but the H row (NVR registers) held across it: no transposed copy of L, no v_readlane chain.
 //   h: row i of the SPD matrix on entry (the FULL row: the trailing block is kept symmetric), destroyed.  Lanes >= nv hold identity
-//   rows.  LDS, private to the lane group: panel (4 G floats), vec (G), save (12 NV4).
+//   rows.  LDS, private to the lane group: panel (4 G floats), vec (G), save (12 NV4, may alias arrays that are dead across the call).
 // Per 4-column block: every lane parks its four raw panel entries and its running right-hand side in LDS (one round trip), refactors
 // the 4 x 4 diagonal block redundantly in registers (no cross-lane traffic), takes its own entries of L and applies the Schur update
-// from the RAW panel (h[k] -= (x Ld^-1) . p_k = L_i . L_k); the forward substitution rides along.  The backward substitution needs
-// columns of L, which live across lanes: per block four DPP reductions of h[c] * x, then the 4 x 4 back substitution in registers
-// from the block factors saved in LDS.  NVR / 4 LDS round trips per factorisation where chol_factor_rows needs NVR, and NVR^2 / 8
-// float4 panel reads where it needs NVR^2 / 2 scalar ones (the G1's 64-lane Newton kernel spent 65 % of its time there).
-DEV float rsqrt_nr(float pv) {  // v_rsq_f32 + one Newton step (~0.5 ulp), as chol_factor_rows
+// from the RAW panel (h[k] -= (x Ld^-1) . p_k = L_i . L_k); the forward substitution L y = g rides along (y_blk = Ld^-1 g_blk,
+// g_i -= L_i,blk . y_blk).  The backward substitution L^T x = y needs columns of L, which live across lanes: per block four DPP
+// reductions of h[c] * x (lanes without an x yet contribute zero), then the 4 x 4 back substitution in registers from the block
+// factors saved in LDS.  NVR / 4 LDS round trips per factorisation and NVR^2 / 8 float4 panel reads, where a pivot-column-at-a-time
+// factorisation needs NVR and NVR^2 / 2 scalar ones (the G1's 64-lane Newton kernel spent 65 % of its time there).
+DEV float rsqrt_nr(float pv) {  // v_rsq_f32 + one Newton step (~0.5 ulp)
   float inv = __builtin_amdgcn_rsqf(pv);
   return inv * (1.5f - 0.5f * pv * inv * inv);
 }
@@ -400,261 +334,6 @@ DEV void euler_advance(const MjhModel& m, const MjhData& d, int w, int lig, bool
     }
   }
   if (lig == 0) d.time[w] += h;
-}
-
-// (cost - cost(0), grad, hess) of ONE constraint row on the ray at step alpha
-// (solver.py:518-556 _compute_efc_eval_pt_pyramidal; alpha = 0 variant 620-647)
-struct P3 {
-  float c, g, h;
-};
-DEV P3 eval_row(float ja, float jv, float D, float f, int kind, float a) {
-  const float jvD = jv * D, hess = jv * jvD, grad0 = jvD * ja;
-  const float x = ja + a * jv;
-  P3 r = P3{0.0f, 0.0f, 0.0f};
-  if (kind == 2) {  // limit / contact: active only when x < 0
-    const float quad0 = 0.5f * D * ja * ja;
-    const float cost0 = ja < 0.0f ? quad0 : 0.0f;
-    if (x < 0.0f) {
-      r.c = a * (grad0 + 0.5f * a * hess) + (quad0 - cost0);
-      r.g = grad0 + a * hess;
-      r.h = hess;
-    } else {
-      r.c = -cost0;
-    }
-  } else if (kind == 1) {  // friction loss
-    const float rf = safe_div(f, D);
-    const float cost0 = (-rf < ja && ja < rf) ? 0.5f * D * ja * ja : (ja <= -rf ? f * (-0.5f * rf - ja) : f * (-0.5f * rf + ja));
-    if (-rf < x && x < rf) {
-      r.c = 0.5f * D * x * x - cost0;
-      r.g = jvD * x;
-      r.h = hess;
-    } else if (x <= -rf) {
-      r.c = f * (-0.5f * rf - x) - cost0;
-      r.g = -f * jv;
-    } else {
-      r.c = f * (-0.5f * rf + x) - cost0;
-      r.g = f * jv;
-    }
-  } else if (kind == 0) {  // equality
-    r.c = a * (grad0 + 0.5f * a * hess);
-    r.g = grad0 + a * hess;
-    r.h = hess;
-  }
-  return r;
-}
-DEV bool in_bracket(P3 x, P3 y) { return (x.g < y.g && y.g < 0.0f) || (x.g > y.g && y.g > 0.0f); }
-
-#ifndef MJH_LS_NOISE_ULPS
-#define MJH_LS_NOISE_ULPS 4
-#endif
-// ---- the line search (solver.py:835-1347) over rows held in registers; every sum of an evaluation round is reduced together
-// HAS_FL: friction-loss rows present (three-zone cost, rare): a compile-time switch, the common instantiation is branch-free
-template <int NR, int G, bool HAS_FL, int RED = 0>
-DEV void line_search_rows(const float (&rja)[NR], const float (&rjv)[NR], const float (&rD)[NR], const int (&rkind)[NR],
-                          const float* floss_lane, float gauss1_lane, float gauss2_lane, float gauss1_abs_lane, float gtol_in, int ls_iterations,
-                          float& alpha_out, float& improvement_out, bool& converged_out, int* iters_out = nullptr) {
-  float ehess[NR], egrad0[NR], ecact[NR], ecin[NR];
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    const float jvD = rjv[k] * rD[k], quad0 = 0.5f * rD[k] * rja[k] * rja[k];
-    const float cost0 = (rkind[k] == 0 || rja[k] < 0.0f) ? quad0 : 0.0f;
-    ehess[k] = rjv[k] * jvD;
-    egrad0[k] = jvD * rja[k];
-    ecact[k] = quad0 - cost0;
-    ecin[k] = -cost0;
-  }
-  auto eval = [&](float a) __attribute__((always_inline)) {
-    P3 s = P3{0.0f, 0.0f, 0.0f};
-    if (!HAS_FL) {
-      const float ha = 0.5f * a;
-#pragma unroll
-      for (int k = 0; k < NR; ++k) {
-        const bool act = rkind[k] == 0 || (rja[k] + a * rjv[k] < 0.0f);
-        s.c += act ? a * (egrad0[k] + ha * ehess[k]) + ecact[k] : ecin[k];
-        s.g += act ? egrad0[k] + a * ehess[k] : 0.0f;
-        s.h += act ? ehess[k] : 0.0f;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NR; ++k) {
-        const P3 t = eval_row(rja[k], rjv[k], rD[k], rkind[k] == 1 ? floss_lane[G * k] : 0.0f, rkind[k], a);
-        s.c += t.c;
-        s.g += t.g;
-        s.h += t.h;
-      }
-    }
-    return s;
-  };
-  const P3 e = eval(0.0f);
-#if MJH_LS_NOISE_ULPS > 0
-  // float32: the ray derivative is a sum of ~nefc + nv terms that mostly cancel at the minimum, so it carries rounding noise of
-  // about eps * sum |term|.  A derivative inside that noise is zero as far as float32 can tell: bracketing on (the reference's
-  // tolerance floor of 1e-6 is an absolute number chosen for float64) only chases noise -- measured 2.5 bracketing iterations
-  // per call against 0.75 for the float64 oracle, with no effect on the iterates.
-  // (round 3: the three sums of the Gauss quadratic -- search . (Ma - qfrc_smooth), search . M search / 2 and the absolute terms of the
-  // first -- ride in the same reduction: one dependent DPP chain per solver iteration less)
-  float eabs = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NR; ++k) eabs += fabsf(egrad0[k]);
-  float r2[6] = {e.g, e.h, eabs, gauss1_lane, gauss2_lane, gauss1_abs_lane};
-  gsum_sel<G, 6, RED>(r2);
-  const float gauss1 = r2[3], gauss2 = r2[4];
-  const float gtol = fmaxf(gtol_in, (MJH_LS_NOISE_ULPS * 5.96e-8f) * (r2[5] + r2[2]));
-#else
-  float r2[4] = {e.g, e.h, gauss1_lane, gauss2_lane};
-  gsum_sel<G, 4, RED>(r2);
-  const float gauss1 = r2[2], gauss2 = r2[3];
-  const float gtol = gtol_in;
-#endif
-  // group sums + the Gauss (smooth) quadratic; the sums of up to three ray points are reduced together (gsumg_n)
-  auto finish = [&](float c, float g, float h, float a) __attribute__((always_inline)) {
-    return P3{a * a * gauss2 + a * gauss1 + c, 2.0f * a * gauss2 + gauss1 + g, 2.0f * gauss2 + h};
-  };
-  const P3 p0 = P3{0.0f, gauss1 + r2[0], 2.0f * gauss2 + r2[1]};
-  const float lo_alpha_in = -fast_div(p0.g, p0.h);
-  const P3 el = eval(lo_alpha_in);
-  float r3[3] = {el.c, el.g, el.h};
-  gsum_sel<G, 3, RED>(r3);
-  const P3 lo_in = finish(r3[0], r3[1], r3[2], lo_alpha_in);
-  float alpha = 0.0f, improvement = 0.0f;
-  bool ls_converged = fabsf(lo_in.g) < gtol && lo_in.c < 0.0f;
-  if (ls_converged) {
-    alpha = lo_alpha_in;
-    improvement = -lo_in.c;
-  } else {
-    const bool lo_less = lo_in.g < p0.g;
-    P3 lo = lo_less ? lo_in : p0, hi = lo_less ? p0 : lo_in;
-    float lo_alpha = lo_less ? lo_alpha_in : 0.0f, hi_alpha = lo_less ? 0.0f : lo_alpha_in;
-    for (int it = 0; it < ls_iterations; ++it) {
-      if (iters_out) ++*iters_out;
-      const float a_lo = lo_alpha - fast_div(lo.g, lo.h), a_hi = hi_alpha - fast_div(hi.g, hi.h);
-      const float a_mid = 0.5f * (lo_alpha + hi_alpha);
-      const P3 e1 = eval(a_lo), e2 = eval(a_hi), e3 = eval(a_mid);
-      float r9[9] = {e1.c, e1.g, e1.h, e2.c, e2.g, e2.h, e3.c, e3.g, e3.h};
-      gsum_sel<G, 9, RED>(r9);
-      const P3 lo_next = finish(r9[0], r9[1], r9[2], a_lo), hi_next = finish(r9[3], r9[4], r9[5], a_hi), mid = finish(r9[6], r9[7], r9[8], a_mid);
-      // Bracket update (solver.py:1222-1290).  The reference takes a candidate when its derivative lies strictly between the
-      // bracket end's derivative and zero, for three candidates in turn -- each test on the end the previous one may have
-      // replaced.  The end therefore finishes on the candidate whose derivative is closest to zero among those strictly
-      // between the ORIGINAL end and zero (the earliest on ties), which needs no chain: three keys, one minimum, one select.
-      auto pick = [](P3& end, float& end_a, const P3& y1, float a1, const P3& y2, float a2, const P3& y3, float a3) __attribute__((always_inline)) {
-        const float g0 = end.g, m0 = fabsf(g0);
-        auto key = [&](float g) __attribute__((always_inline)) {
-          const float mg = fabsf(g);
-          const bool same = (__float_as_int(g) ^ __float_as_int(g0)) >= 0;  // equal sign bits
-          return (same && mg > 0.0f && mg < m0) ? mg : 3.0e38f;
-        };
-        const float k1 = key(y1.g), k2 = key(y2.g), k3 = key(y3.g);
-        const float kb = fminf(k1, fminf(k2, k3));
-        const bool any = kb < 3.0e38f;
-        const bool u1 = k1 == kb, u2 = k2 == kb;
-        const float sc = u1 ? y1.c : (u2 ? y2.c : y3.c), sg = u1 ? y1.g : (u2 ? y2.g : y3.g), sh = u1 ? y1.h : (u2 ? y2.h : y3.h);
-        const float sa = u1 ? a1 : (u2 ? a2 : a3);
-        end.c = any ? sc : end.c;
-        end.g = any ? sg : end.g;
-        end.h = any ? sh : end.h;
-        end_a = any ? sa : end_a;
-        return any;
-      };
-      const bool swap_lo = pick(lo, lo_alpha, lo_next, a_lo, mid, a_mid, hi_next, a_hi);
-      const bool swap_hi = pick(hi, hi_alpha, hi_next, a_hi, mid, a_mid, lo_next, a_lo);
-      const bool ls_done = (!swap_lo && !swap_hi) || (lo.c < 0.0f && lo.g < 0.0f && lo.g > -gtol) || (hi.c < 0.0f && hi.g > 0.0f && hi.g < gtol);
-      const bool improved = lo.c < 0.0f || hi.c < 0.0f;
-      const bool lo_better = lo.c < hi.c;
-      alpha = improved ? (lo_better ? lo_alpha : hi_alpha) : alpha;
-      improvement = improved ? -(lo_better ? lo.c : hi.c) : improvement;
-      if (ls_done) {
-        ls_converged = true;
-        break;
-      }
-    }
-  }
-  alpha_out = alpha;
-  improvement_out = improvement;
-  converged_out = ls_converged;
-}
-
-// ---- elliptic friction cones (solver.py:272-421) -------------------------------------------------------------
-// One contact = `dim` consecutive rows (normal, then friction directions).  In the reference's scaled coordinates
-// N = mu * Jaref_0 and T = |(fri_j * Jaref_j)_j>=1| the contact is SATISFIED for N >= mu T (top zone), QUADRATIC for
-// mu N + T <= 0 (bottom zone, every row an independent quadratic) and in the CONE (middle) zone otherwise, where its cost is
-// dm/2 (N - mu T)^2, dm = D_0 / (mu^2 (1 + mu^2)), mu = friction_0 / sqrt(impratio).
-DEV int ell_zone(float mu, float N, float T) {
-  if (N >= mu * T || (T <= 0.0f && N >= 0.0f)) return ST_SATISFIED;
-  if (mu * N + T <= 0.0f || (T <= 0.0f && N < 0.0f)) return ST_QUADRATIC;
-  return ST_CONE;
-}
-// constants of one contact on the search ray, held by the lane that owns the contact's first row
-struct EllRay {
-  float mu, dm, q0, q1, q2, u0, v0, uu, uv, vv;  // q = sum_j (D ja^2 / 2, D jv ja, D jv^2 / 2); u = scaled Jaref, v = scaled jv
-  float cost0, T0, r0;                            // the reference point alpha = 0 (_eval_elliptic_reference solver.py:275-298)
-  int state0;
-};
-DEV void ell_ray_reference(EllRay& e) {
-  e.T0 = 0.0f;
-  e.r0 = 0.0f;
-  if (e.uu <= 0.0f) {
-    e.state0 = e.u0 < 0.0f ? ST_QUADRATIC : ST_SATISFIED;
-    e.cost0 = e.u0 < 0.0f ? e.q0 : 0.0f;
-    return;
-  }
-  e.T0 = sqrtf(e.uu);
-  if (e.u0 >= e.mu * e.T0) {
-    e.state0 = ST_SATISFIED;
-    e.cost0 = 0.0f;
-  } else if (e.mu * e.u0 + e.T0 <= 0.0f) {
-    e.state0 = ST_QUADRATIC;
-    e.cost0 = e.q0;
-  } else {
-    e.r0 = e.u0 - e.mu * e.T0;
-    e.state0 = ST_CONE;
-    e.cost0 = 0.5f * e.dm * e.r0 * e.r0;
-  }
-}
-// (cost(alpha) - cost(0), d/dalpha, d2/dalpha2) of one elliptic contact: the shifted forms of the reference
-// (_eval_elliptic_shifted solver.py:343-403), which difference against the reference point analytically -- in float32
-// the plain difference of two costs loses the line search's whole signal near convergence
-DEV P3 ell_eval(const EllRay& e, float a) {
-  const float N = e.u0 + a * e.v0;
-  const float Td = a * (2.0f * e.uv + a * e.vv), Tsqr = e.uu + Td;
-  const float aq2 = a * e.q2;
-  bool quadz = false, conez = false;
-  float T = 0.0f;
-  if (Tsqr <= 0.0f) {
-    quadz = N < 0.0f;
-  } else {
-    T = sqrtf(Tsqr);
-    if (N >= e.mu * T) {
-    } else if (e.mu * N + T <= 0.0f) quadz = true;
-    else conez = true;
-  }
-  if (quadz) {  // _eval_elliptic_quadratic_shifted solver.py:318-340
-    float cost = a * (aq2 + e.q1);
-    if (e.state0 == ST_CONE) {
-      const float b0 = e.mu * e.u0 + e.T0;
-      cost += 0.5f * e.dm * b0 * b0;
-    } else if (e.state0 == ST_SATISFIED) {
-      cost = 0.5f * e.dm * (1.0f + e.mu * e.mu) * (N * N + fmaxf(Tsqr, 0.0f));
-    }
-    return P3{cost, 2.0f * aq2 + e.q1, 2.0f * e.q2};
-  }
-  if (conez) {
-    const float Tinv = 1.0f / T;
-    const float T1 = (e.uv + a * e.vv) * Tinv, T2 = (e.vv - T1 * T1) * Tinv;
-    const float r = N - e.mu * T, r1 = e.v0 - e.mu * T1;
-    float cost;
-    if (e.state0 == ST_CONE) {  // rationalised T - T0
-      const float Tdelta = Td / (T + e.T0), rdelta = a * e.v0 - e.mu * Tdelta;
-      cost = 0.5f * e.dm * rdelta * (2.0f * e.r0 + rdelta);
-    } else if (e.state0 == ST_QUADRATIC) {
-      const float b = e.mu * N + T;
-      cost = a * (aq2 + e.q1) - 0.5f * e.dm * b * b;
-    } else {
-      cost = 0.5f * e.dm * r * r;
-    }
-    return P3{cost, e.dm * r * r1, e.dm * (r1 * r1 - e.mu * r * T2)};
-  }
-  return P3{-e.cost0, 0.0f, 0.0f};
 }
 
 // Rows of M^-1 by Gauss-Jordan with lane i owning row i of [A | B] (A = M, B = I); no pivoting (M is SPD).
@@ -1303,26 +982,19 @@ DEV void solve_body(const MjhModel& m, const MjhData& d, float* smem, const Blk&
     } else {
       gsumg_n<G, 3>(gs);
       const float gauss1 = gs[0], gauss2 = gs[1];
-      // per-row constants of the ray (solver.py:518-556): cost(a) - cost(0) = a (grad0 + a hess / 2) + cact when the
-      // row is active at a, cin otherwise; equality rows are always active, padding rows have D = jv = 0
-      float ehess[NR], egrad0[NR], ecact[NR], ecin[NR];
+      // the rows' constants on the ray; every row also publishes its terms to its contact (an elliptic contact is evaluated by its
+      // first row's lane) and the rows of an elliptic contact then drop out of the per-row sum
+      RowRay<NR> rows;
+      row_ray(rows, rja, rjv, rD, rkind);
 #pragma unroll
       for (int k = 0; k < NR; ++k) {
-        const float jvD = rjv[k] * rD[k], quad0 = 0.5f * rD[k] * rja[k] * rja[k];
-        const float cost0 = (rkind[k] == 0 || rja[k] < 0.0f) ? quad0 : 0.0f;
-        ehess[k] = rjv[k] * jvD;
-        egrad0[k] = jvD * rja[k];
-        ecact[k] = quad0 - cost0;
-        ecin[k] = -cost0;
-        if (ELL) {  // every row of an elliptic contact publishes its terms; the contact is evaluated by its first row's lane
-          const int r = lig + G * k;
-          exu[r] = rja[k] * rs[k];
-          exv[r] = rjv[k] * rs[k];
-          exq0[r] = quad0;
-          exq1[r] = egrad0[k];
-          exq2[r] = 0.5f * ehess[k];
-          if (rkind[k] >= 4) ehess[k] = egrad0[k] = ecact[k] = ecin[k] = 0.0f;
-        }
+        const int r = lig + G * k;
+        exu[r] = rja[k] * rs[k];
+        exv[r] = rjv[k] * rs[k];
+        exq0[r] = 0.5f * rD[k] * rja[k] * rja[k];
+        exq1[r] = rows.grad0[k];
+        exq2[r] = 0.5f * rows.hess[k];
+        if (rkind[k] >= 4) rows.hess[k] = rows.grad0[k] = rows.cact[k] = rows.cin[k] = 0.0f;
       }
       EllRay ray[NR];
       if (ELL) {
@@ -1354,87 +1026,33 @@ DEV void solve_body(const MjhModel& m, const MjhData& d, float* smem, const Blk&
       }
       auto eval = [&](float a) __attribute__((always_inline)) {
         P3 s = P3{0.0f, 0.0f, 0.0f};
-        if (ELL) {
 #pragma unroll
-          for (int k = 0; k < NR; ++k)
-            if (rkind[k] == 4) {
-              const P3 t = ell_eval(ray[k], a);
-              s.c += t.c;
-              s.g += t.g;
-              s.h += t.h;
-            }
-        }
-        if (!has_fl) {  // equality / limit / contact rows only: branch-free
-          const float ha = 0.5f * a;
-#pragma unroll
-          for (int k = 0; k < NR; ++k) {
-            const bool act = rkind[k] == 0 || (rja[k] + a * rjv[k] < 0.0f);  // (elliptic rows: all four terms are zero)
-            s.c += act ? a * (egrad0[k] + ha * ehess[k]) + ecact[k] : ecin[k];
-            s.g += act ? egrad0[k] + a * ehess[k] : 0.0f;
-            s.h += act ? ehess[k] : 0.0f;
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < NR; ++k) {
-            const P3 t = eval_row(rja[k], rjv[k], rD[k], rkind[k] == 1 ? floss[lig + G * k] : 0.0f, rkind[k], a);
+        for (int k = 0; k < NR; ++k)
+          if (rkind[k] == 4) {
+            const P3 t = ell_eval(ray[k], a);
             s.c += t.c;
             s.g += t.g;
             s.h += t.h;
           }
-        }
+        if (!has_fl) row_ray_eval(s, rows, rja, rjv, rkind, a);  // (elliptic rows: all four constants are zero)
+        else row_ray_eval_fl<NR, G>(s, rja, rjv, rD, rkind, floss + lig, a);
         return s;
-      };
-      // group sums + the Gauss (smooth) quadratic
-      auto total = [&](P3 s, float a) __attribute__((always_inline)) {
-        return P3{a * a * gauss2 + a * gauss1 + gsumg<G>(s.c), 2.0f * a * gauss2 + gauss1 + gsumg<G>(s.g), 2.0f * gauss2 + gsumg<G>(s.h)};
       };
       const P3 e = eval(0.0f);
       const P3 p0 = P3{0.0f, gauss1 + gsumg<G>(e.g), 2.0f * gauss2 + gsumg<G>(e.h)};
-      const float lo_alpha_in = -fast_div(p0.g, p0.h);
-      const P3 lo_in = total(eval(lo_alpha_in), lo_alpha_in);
-      ls_converged = fabsf(lo_in.g) < gtol && lo_in.c < 0.0f;
-      if (ls_converged) {
-        alpha = lo_alpha_in;
-        improvement = -lo_in.c;
-      } else {
-        const bool lo_less = lo_in.g < p0.g;
-        P3 lo = lo_less ? lo_in : p0, hi = lo_less ? p0 : lo_in;
-        float lo_alpha = lo_less ? lo_alpha_in : 0.0f, hi_alpha = lo_less ? 0.0f : lo_alpha_in;
-        for (int it = 0; it < ls_iterations; ++it) {
-          const float a_lo = lo_alpha - fast_div(lo.g, lo.h), a_hi = hi_alpha - fast_div(hi.g, hi.h);
-          const float a_mid = 0.5f * (lo_alpha + hi_alpha);
-          const P3 lo_next = total(eval(a_lo), a_lo), hi_next = total(eval(a_hi), a_hi), mid = total(eval(a_mid), a_mid);
-          // conditional moves, not branches: the six updates are wave-divergent between the two worlds of a wavefront
-          auto take = [](bool c, P3& dst, float& da, const P3& src, float sa) __attribute__((always_inline)) {
-            dst.c = c ? src.c : dst.c;
-            dst.g = c ? src.g : dst.g;
-            dst.h = c ? src.h : dst.h;
-            da = c ? sa : da;
-          };
-          const bool s1 = in_bracket(lo, lo_next);
-          take(s1, lo, lo_alpha, lo_next, a_lo);
-          const bool s2 = in_bracket(lo, mid);
-          take(s2, lo, lo_alpha, mid, a_mid);
-          const bool s3 = in_bracket(lo, hi_next);
-          take(s3, lo, lo_alpha, hi_next, a_hi);
-          const bool h1 = in_bracket(hi, hi_next);
-          take(h1, hi, hi_alpha, hi_next, a_hi);
-          const bool h2 = in_bracket(hi, mid);
-          take(h2, hi, hi_alpha, mid, a_mid);
-          const bool h3 = in_bracket(hi, lo_next);
-          take(h3, hi, hi_alpha, lo_next, a_lo);
-          const bool swap_lo = s1 || s2 || s3, swap_hi = h1 || h2 || h3;
-          const bool ls_done = (!swap_lo && !swap_hi) || (lo.c < 0.0f && lo.g < 0.0f && lo.g > -gtol) || (hi.c < 0.0f && hi.g > 0.0f && hi.g < gtol);
-          const bool improved = lo.c < 0.0f || hi.c < 0.0f;
-          const bool lo_better = lo.c < hi.c;
-          alpha = improved ? (lo_better ? lo_alpha : hi_alpha) : alpha;
-          improvement = improved ? -(lo_better ? lo.c : hi.c) : improvement;
-          if (ls_done) {
-            ls_converged = true;
-            break;
-          }
+      // group sums + the Gauss (smooth) quadratic
+      auto totals = [&](const auto& a, auto& t) __attribute__((always_inline)) {
+        constexpr int N = sizeof(a) / sizeof(a[0]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const P3 s = eval(a[i]);
+          t[i] = P3{a[i] * a[i] * gauss2 + a[i] * gauss1 + gsumg<G>(s.c), 2.0f * a[i] * gauss2 + gauss1 + gsumg<G>(s.g), 2.0f * gauss2 + gsumg<G>(s.h)};
         }
-      }
+      };
+      const LsStep ls = ls_bracket(p0, gtol, ls_iterations, totals);  // (the reference's gtol: no float32 noise floor here, see linesearch.hpp)
+      alpha = ls.alpha;
+      improvement = ls.improvement;
+      ls_converged = ls.converged;
     }
     if (!ls_converged) ovf |= OVF_LS_ITERATIONS;
     pc.mark(6);

@@ -388,7 +388,7 @@ DEV void solve_big_body(const MjhModel& m, const MjhData& d, float* smem, const 
         const int kr = kind[r] & 7;
         if (kr == 5) continue;  // (evaluated with its contact by the first row's lane)
         P3 t;
-        if (kr == 4) {  // the contact's ray constants (solver.hpp EllRay), then the reference's shifted forms
+        if (kr == 4) {  // the contact's ray constants (linesearch.hpp EllRay), then the reference's shifted forms
           const int dim = rcon[r] >> 16;
           EllRay e;
           e.mu = rmu[r];
@@ -421,52 +421,14 @@ DEV void solve_big_body(const MjhModel& m, const MjhData& d, float* smem, const 
     };
     P3 p0 = total(0.0f);
     p0.c = 0.0f;
-    const float lo_alpha_in = -fast_div(p0.g, p0.h);
-    const P3 lo_in = total(lo_alpha_in);
-    float alpha = 0.0f;
-    improvement = 0.0f;
-    bool ls_converged = fabsf(lo_in.g) < gtol && lo_in.c < 0.0f;
-    if (ls_converged) {
-      alpha = lo_alpha_in;
-      improvement = -lo_in.c;
-    } else {
-      const bool lo_less = lo_in.g < p0.g;
-      P3 lo = lo_less ? lo_in : p0, hi = lo_less ? p0 : lo_in;
-      float lo_alpha = lo_less ? lo_alpha_in : 0.0f, hi_alpha = lo_less ? 0.0f : lo_alpha_in;
-      for (int it = 0; it < ls_iterations; ++it) {
-        const float a_lo = lo_alpha - fast_div(lo.g, lo.h), a_hi = hi_alpha - fast_div(hi.g, hi.h);
-        const float a_mid = 0.5f * (lo_alpha + hi_alpha);
-        const P3 lo_next = total(a_lo), hi_next = total(a_hi), mid = total(a_mid);
-        auto take = [](bool c, P3& dst, float& da_, const P3& src, float sa) __attribute__((always_inline)) {
-          dst.c = c ? src.c : dst.c;
-          dst.g = c ? src.g : dst.g;
-          dst.h = c ? src.h : dst.h;
-          da_ = c ? sa : da_;
-        };
-        const bool s1 = in_bracket(lo, lo_next);
-        take(s1, lo, lo_alpha, lo_next, a_lo);
-        const bool s2 = in_bracket(lo, mid);
-        take(s2, lo, lo_alpha, mid, a_mid);
-        const bool s3 = in_bracket(lo, hi_next);
-        take(s3, lo, lo_alpha, hi_next, a_hi);
-        const bool h1 = in_bracket(hi, hi_next);
-        take(h1, hi, hi_alpha, hi_next, a_hi);
-        const bool h2 = in_bracket(hi, mid);
-        take(h2, hi, hi_alpha, mid, a_mid);
-        const bool h3 = in_bracket(hi, lo_next);
-        take(h3, hi, hi_alpha, lo_next, a_lo);
-        const bool swap_lo = s1 || s2 || s3, swap_hi = h1 || h2 || h3;
-        const bool ls_done = (!swap_lo && !swap_hi) || (lo.c < 0.0f && lo.g < 0.0f && lo.g > -gtol) || (hi.c < 0.0f && hi.g > 0.0f && hi.g < gtol);
-        const bool improved = lo.c < 0.0f || hi.c < 0.0f;
-        const bool lo_better = lo.c < hi.c;
-        alpha = improved ? (lo_better ? lo_alpha : hi_alpha) : alpha;
-        improvement = improved ? -(lo_better ? lo.c : hi.c) : improvement;
-        if (ls_done) {
-          ls_converged = true;
-          break;
-        }
-      }
-    }
+    auto totals = [&](const auto& a, auto& t) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < (int)(sizeof(a) / sizeof(a[0])); ++i) t[i] = total(a[i]);
+    };
+    const LsStep ls = ls_bracket(p0, gtol, ls_iterations, totals);  // (the reference's gtol: no float32 noise floor here, see linesearch.hpp)
+    const float alpha = ls.alpha;
+    improvement = ls.improvement;
+    const bool ls_converged = ls.converged;
     if (!ls_converged) ovf |= OVF_LS_ITERATIONS;
     // ---- move along the ray ---------------------------------------------------------------------------------------
     for (int i = lig; i < nv; i += G) {

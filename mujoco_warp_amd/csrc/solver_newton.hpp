@@ -14,9 +14,10 @@
 //     leave column i (= row i, H is symmetric) of world b's H in lane (b, i).  Per row: two LDS reads, one multiply, one
 //     select; the VALU version needed 16 LDS reads and 60 FMAs per row pair.  f32 MFMA is bitwise an fmaf chain (k-ordered),
 //     so the result is an ordinary float32 sum in row order.
-//   * the Cholesky is right-looking over 4-column blocks: one LDS panel write per block, every lane refactors the 4x4
-//     diagonal block redundantly in registers (no cross-lane traffic) and applies the Schur update from the raw panel:
-//     7 LDS round trips per factorisation instead of 28.
+//   * the Cholesky (chol_factor_solve_g<NV4, 32>, solver.hpp) is right-looking over 4-column blocks: one LDS panel write per
+//     block, every lane refactors the 4x4 diagonal block redundantly in registers (no cross-lane traffic) and applies the Schur
+//     update from the raw panel: 7 LDS round trips per factorisation instead of 28.
+//   * the line search is line_search_rows (linesearch.hpp), as in solve_body.
 //   * register discipline: the only long-lived array is the M row (28); factorisation, forward and backward substitution
 //     are one routine that holds nothing but the H row (no transposed copy of L): <= 168 VGPRs = three wavefronts per SIMD.
 //   * LDS decides the rest: the two worlds of a wavefront share ONE pool of J rows sized for the steady state (the humanoid
@@ -58,107 +59,6 @@ __host__ __device__ inline int newton_min_pool(int njmax) {
   return (2 * 4 * NV4 > one ? 2 * 4 * NV4 : one);
 }
 
-// x = H^-1 g by a blocked right-looking Cholesky with lane i owning row i (NVR <= 32) -- factorisation, forward and backward
-// substitution in one routine, nothing but the H row (NVR registers) held across it.
-//   h: row i of the SPD matrix on entry (the FULL row: the trailing block is kept symmetric), destroyed.  Lanes >= nv hold
-//   identity rows.  LDS, private to the 32-lane group: panel (128 floats), vec (32), save (12 NV4, may alias dead arrays).
-// Per 4-column block: every lane parks its four raw panel entries and its running right-hand side in LDS (one round trip),
-// refactors the 4x4 diagonal block redundantly in registers (no cross-lane traffic), takes its own entries of L and applies
-// the Schur update from the RAW panel (h[k] -= (x Ld^-1) . p_k = L_i . L_k); the forward substitution L y = g rides along
-// (y_blk = Ld^-1 g_blk, g_i -= L_i,blk . y_blk).  The backward substitution L^T x = y needs columns of L, which live
-// across lanes: per block four 32-lane DPP reductions of h[c] * x (lanes without an x yet contribute zero), then the 4x4
-// back substitution in registers from the block factors saved in LDS.  No transposed copy of L, no v_readlane chain.
-template <int NV4>
-DEV float chol_factor_solve(float (&h)[4 * NV4], float g, float* panel, float* vec, float* save, int lig) {
-  constexpr int NVR = 4 * NV4, G = 32;
-  float gacc = g, y = 0.0f;
-#pragma unroll
-  for (int jb = 0; jb < NV4; ++jb) {
-    const int j0 = 4 * jb;
-    gsync();  // the previous block's panel reads are issued before this write (one wavefront: LDS ops complete in order)
-    // unconditional (lanes >= NVR park junk in their own slot): a branch here splits the block, the compiler then sinks the
-    // previous block's Schur FMAs past it while their panel loads must stay before this write -- 96 VGPRs held, spilled
-    *reinterpret_cast<float4*>(panel + 4 * lig) = make_float4(h[j0], h[j0 + 1], h[j0 + 2], h[j0 + 3]);
-    vec[lig] = gacc;
-    gsync();
-    // 4x4 diagonal block (rows j0..j0+3 of the panel), factored redundantly by every lane
-    const float4 d0 = *reinterpret_cast<const float4*>(panel + 4 * j0);
-    const float4 d1 = *reinterpret_cast<const float4*>(panel + 4 * (j0 + 1));
-    const float4 d2 = *reinterpret_cast<const float4*>(panel + 4 * (j0 + 2));
-    const float4 d3 = *reinterpret_cast<const float4*>(panel + 4 * (j0 + 3));
-    const float4 g4 = *reinterpret_cast<const float4*>(vec + j0);
-    const float r0 = rsqrt_nr(fmaxf(d0.x, MJ_MINVAL));
-    const float l10 = d1.x * r0, l20 = d2.x * r0, l30 = d3.x * r0;
-    const float r1 = rsqrt_nr(fmaxf(d1.y - l10 * l10, MJ_MINVAL));
-    const float l21 = (d2.y - l20 * l10) * r1, l31 = (d3.y - l30 * l10) * r1;
-    const float r2 = rsqrt_nr(fmaxf(d2.z - l20 * l20 - l21 * l21, MJ_MINVAL));
-    const float l32 = (d3.z - l30 * l20 - l31 * l21) * r2;
-    const float r3 = rsqrt_nr(fmaxf(d3.w - l30 * l30 - l31 * l31 - l32 * l32, MJ_MINVAL));
-    // (every lane stores the same twelve words: the block factors the backward pass needs again)
-    *reinterpret_cast<float4*>(save + 12 * jb) = make_float4(l10, l20, l30, r0);
-    *reinterpret_cast<float4*>(save + 12 * jb + 4) = make_float4(l21, l31, l32, r1);
-    *reinterpret_cast<float2*>(save + 12 * jb + 8) = make_float2(r2, r3);
-    // this lane's entries of L in the block's columns: x = p Ld^-T (for the block's own lanes: the rows of Ld)
-    const float x0 = h[j0] * r0;
-    const float x1 = (h[j0 + 1] - x0 * l10) * r1;
-    const float x2 = (h[j0 + 2] - x0 * l20 - x1 * l21) * r2;
-    const float x3 = (h[j0 + 3] - x0 * l30 - x1 * l31 - x2 * l32) * r3;
-    h[j0] = x0;
-    h[j0 + 1] = x1;
-    h[j0 + 2] = x2;
-    h[j0 + 3] = x3;
-    // forward substitution of the block, then this lane's right-hand side loses the block's contribution
-    const float y0 = g4.x * r0;
-    const float y1 = (g4.y - l10 * y0) * r1;
-    const float y2 = (g4.z - l20 * y0 - l21 * y1) * r2;
-    const float y3 = (g4.w - l30 * y0 - l31 * y1 - l32 * y2) * r3;
-    y = lig == j0 ? y0 : y;  // (four selects: a nested conditional becomes branches)
-    y = lig == j0 + 1 ? y1 : y;
-    y = lig == j0 + 2 ? y2 : y;
-    y = lig == j0 + 3 ? y3 : y;
-    gacc -= x0 * y0 + x1 * y1 + x2 * y2 + x3 * y3;
-    if (jb + 1 < NV4) {
-      // Schur update of the trailing rows from the RAW panel: h[k] -= (x Ld^-1) . p_k  (= L_i . L_k)
-      const float u3 = x3 * r3;
-      const float u2 = (x2 - l32 * u3) * r2;
-      const float u1 = (x1 - l21 * u2 - l31 * u3) * r1;
-      const float u0 = (x0 - l10 * u1 - l20 * u2 - l30 * u3) * r0;
-#pragma unroll
-      for (int k = j0 + 4; k < NVR; ++k) {
-        const float4 pk = *reinterpret_cast<const float4*>(panel + 4 * k);
-        h[k] = fmaf(-u3, pk.w, fmaf(-u2, pk.z, fmaf(-u1, pk.y, fmaf(-u0, pk.x, h[k]))));
-      }
-      __builtin_amdgcn_sched_barrier(0);  // finish the update here: deferring it keeps the panel rows in registers
-    }
-  }
-  // ---- backward substitution ------------------------------------------------------------------------------------------
-  gsync();
-  vec[lig] = y;
-  gsync();
-  float x = 0.0f;  // lanes >= NVR never receive a value: their (junk but finite) h entries are multiplied by zero
-#pragma unroll
-  for (int jb = NV4 - 1; jb >= 0; --jb) {
-    const int j0 = 4 * jb;
-    float t4[4] = {h[j0] * x, h[j0 + 1] * x, h[j0 + 2] * x, h[j0 + 3] * x};
-    gsumg_n<G, 4>(t4);
-    const float t0 = t4[0], t1 = t4[1], t2 = t4[2], t3 = t4[3];
-    const float4 y4 = *reinterpret_cast<const float4*>(vec + j0);
-    const float4 sa = *reinterpret_cast<const float4*>(save + 12 * jb);      // l10 l20 l30 r0
-    const float4 sb = *reinterpret_cast<const float4*>(save + 12 * jb + 4);  // l21 l31 l32 r1
-    const float2 sc = *reinterpret_cast<const float2*>(save + 12 * jb + 8);  // r2 r3
-    const float x3 = (y4.w - t3) * sc.y;
-    const float x2 = ((y4.z - t2) - sb.z * x3) * sc.x;
-    const float x1 = ((y4.y - t1) - sb.x * x2 - sb.y * x3) * sb.w;
-    const float x0 = ((y4.x - t0) - sa.x * x1 - sa.y * x2 - sa.z * x3) * sa.w;
-    x = lig == j0 ? x0 : x;
-    x = lig == j0 + 1 ? x1 : x;
-    x = lig == j0 + 2 ? x2 : x;
-    x = lig == j0 + 3 ? x3 : x;
-  }
-  return x;
-}
-
-// exact line search on the convex cost of ONE world (solver.py:835-1347), rows and sums in registers; the same arithmetic as
 DEV bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 
 // Global accesses with a uniform base and a 32-bit per-lane BYTE offset: one VGPR per address (saddr + voffset form) instead
@@ -242,7 +142,7 @@ DEV void newton_pair(const MjhModel& m, const MjhData& d, float* S, const Newton
   if (wave_any(cold)) {
 #pragma unroll
     for (int c = 0; c < NVR; ++c) h[c] = mrow[c];
-    qs = chol_factor_solve<NV4>(h, fs, panel, bvec, save, lig);
+    qs = chol_factor_solve_g<NV4, G>(h, fs, panel, bvec, save, lig);
     if (!active) qs = 0.0f;
   }
   float q = 0.0f;
@@ -395,7 +295,7 @@ DEV void newton_pair(const MjhModel& m, const MjhData& d, float* S, const Newton
     }
     pc.mark(11);
     gsync();  // (eda is read by the H build above; the block factors overwrite it)
-    Mg = chol_factor_solve<NV4>(h, g, panel, bvec, save, lig);
+    Mg = chol_factor_solve_g<NV4, G>(h, g, panel, bvec, save, lig);
     pc.mark(12);
     if (!active) Mg = 0.0f;
     const float srch_new = -Mg;

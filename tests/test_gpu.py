@@ -1426,3 +1426,36 @@ def test_graph_replay_with_sleep_sensors_and_energy():
       a, b = getattr(da, f).numpy(), getattr(db, f).numpy()
       assert (a == b).all(), f
     assert mjm.nsensor == 0 or np.abs(da.sensordata.numpy()).max() > 0
+
+
+import solver_families as sf  # noqa: E402
+
+
+@pytest.mark.parametrize("case", sorted(sf.CASES))
+def test_line_search_loop_is_live_in_every_solver_family(case):
+  """Every solver mapping runs the ONE bracketing loop of csrc/linesearch.hpp (ls_bracket), so the parity tests of a mapping cover it only
+  if that mapping's searches get past the Newton point.  For the smallest scene of the suite that reaches each mapping (solver_families.py), in
+  a state with active contacts: `solver_kernel` names the mapping; with the model's own ls_iterations no search runs out of iterations;
+  and capping ls_iterations at 1 changes qacc of the same state, i.e. some search of this solve took more than one round of the loop."""
+  from mujoco_warp_amd._abi import dev_knobs
+
+  family, mjm, m, d, knobs = sf.device(case)
+  state = {f: getattr(d, f).numpy().copy() for f in ("qpos", "qvel", "qacc_warmstart", "ctrl", "act") if getattr(d, f).size}
+  assert (d.nefc.numpy() > 0).any()
+
+  def solve(ls_iterations):
+    m.opt.ls_iterations = ls_iterations
+    for f, v in state.items():
+      getattr(d, f).assign(v)
+    d.overflow.assign(np.zeros(d.nworld, dtype=np.int32))
+    mjw.forward(m, d)
+    return d.qacc.numpy().copy(), d.overflow.numpy().copy(), d.solver_niter.numpy().copy()
+
+  with dev_knobs(**knobs):
+    assert mjw.solver_kernel(m, d) == family
+    qacc, ovf, niter = solve(int(mjm.opt.ls_iterations))
+    qacc1, _, _ = solve(1)
+  print(f"{case}: nefc {d.nefc.numpy().tolist()} niter {niter.tolist()} overflow {ovf.tolist()} max |qacc - qacc(ls_iterations = 1)| {np.abs(qacc - qacc1).max():.3g}")
+  assert np.isfinite(qacc).all() and (niter > 0).any()
+  assert not (ovf & int(mjw.OverflowType.LS_ITERATIONS)).any(), ovf
+  assert not np.array_equal(qacc, qacc1)

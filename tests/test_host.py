@@ -635,3 +635,50 @@ def test_dev_knobs_refuses_to_shadow_an_environment_value(monkeypatch):
   with pytest.raises(_abi.EngineError, match="MJH_CG_KERNEL"):
     with _abi.dev_knobs(MJH_CG_KERNEL="pair"):
       pass
+
+
+def test_bracket_update_selects_what_the_reference_chain_selects(tmp_path):
+  """linesearch.hpp's bracket_update (three keys, one minimum, one select) against the reference's chained in_bracket / take update
+  (solver.py:1222-1290), compiled for the host from the header the kernels include: tests/ls_bracket_host.cpp walks 17^4 derivative
+  quadruples (end, y1, y2, y3) -- both signs and both zeros, a denormal, ties, candidates beyond the end and on the far side of zero,
+  +-inf, NaN, magnitudes just below the key's sentinel 3.0e38 -- and the selected candidate (c, g, h, alpha) and the flag must be
+  bitwise equal in every one of them."""
+  import shutil
+  import subprocess
+
+  rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+  cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or (rocm_clang if os.path.exists(rocm_clang) else None)
+  assert cxx, "no host C++ compiler"
+  exe = str(tmp_path / "ls_bracket_host")
+  subprocess.run([cxx, "-std=c++17", "-O1", "-I", _CSRC, "-o", exe, os.path.join(conftest.ROOT, "tests", "ls_bracket_host.cpp")], check=True)
+  p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+  print(p.stdout)
+  mm = re.search(r"^(\d+) cases, (\d+) moved the end, (\d+) differ$", p.stdout, flags=re.M)
+  assert mm, p.stdout + p.stderr
+  assert int(mm.group(1)) == 17 ** 4 and int(mm.group(2)) > 10000  # the whole grid ran, and the update is exercised on it
+  assert int(mm.group(3)) == 0 and p.returncode == 0, p.stdout
+
+
+def test_line_search_loop_and_blocked_cholesky_exist_once():
+  """The bracketing loop of the line search lives in linesearch.hpp's ls_bracket alone: solve_body's elliptic branch (solver.hpp),
+  solve_big_body (solver_big.hpp) and line_search_rows call it and no other file names it; the reference's chained update (in_bracket)
+  is not restated in device code; and the blocked Cholesky exists once (chol_factor_solve_g): neither its 32-lane copy nor the
+  pivot-column routines it replaced are left under csrc/ or tools/."""
+  text = {f: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", t, flags=re.S)) for f, t in _csrc_text().items()}
+  calls = {f: len(re.findall(r"\bls_bracket\(", t)) for f, t in text.items()}
+  assert {f: n for f, n in calls.items() if n} == {"linesearch.hpp": 2, "solver.hpp": 1, "solver_big.hpp": 1}, calls
+  ls = text["linesearch.hpp"]
+  assert len(re.findall(r"DEV LsStep ls_bracket\(", ls)) == 1
+  assert "ls_bracket(" in ls[ls.index("DEV void line_search_rows("):]  # the second mention: line_search_rows' call
+  loops = {f: len(re.findall(r"\bit < ls_iterations\b", t)) for f, t in text.items()}
+  assert {f: n for f, n in loops.items() if n} == {"linesearch.hpp": 1}, loops
+  raw = dict(_csrc_text())
+  for f in raw:
+    assert "in_bracket" not in raw[f], f
+  tools = os.path.join(conftest.ROOT, "tools")
+  for f in sorted(os.listdir(tools)):
+    if os.path.isfile(os.path.join(tools, f)):
+      raw["tools/" + f] = open(os.path.join(tools, f), errors="replace").read()
+  for f, t in raw.items():
+    for gone in ("chol_factor_solve<", "chol_factor_rows", "chol_solve_rows"):
+      assert gone not in t, (f, gone)

@@ -1,4 +1,5 @@
 // ubench_ls.hip -- cycles of one line_search_rows<2, 32> call per wavefront as a function of the bracketing iterations it runs.
+#include "contact_rec.hpp"  // (publish_body: solver_newton.hpp's rider branch names it)
 #include "solver_newton.hpp"
 
 #include <cstdio>
